@@ -1,7 +1,7 @@
 """Benchmark: MT_UBPL training step (2-stack hourglass, 256x256, K=16,
 B=32 per GPU: 16 unlabeled + 16 labeled rows) on the HIP path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU, RCCL)
 
 One step = what projects/MT_UBPL.py:173-339 does for one batch: heatmap
@@ -12,12 +12,16 @@ updates — and under torch.distributed the global-count all-reduce and the
 student-gradient all-reduce.  Inputs (images, keypoints) are synthetic and
 already resident in HBM when timing starts.
 
-Rank 0 prints ONE JSON line (see the driver contract in the task notes):
-value = images/s over all ranks, plus `roofline` for the dominant kernel
-(the 3x3 implicit-GEMM conv forward on the f32 matrix cores, timed per
-launch with HIP events on its stream inside the timed region) and
-`cpu_baseline` (the oracle's CPU restatement of the same step on a bounded
-sample, host threads stated).
+Rank 0 prints ONE JSON line: value = images/s over all ranks and ms_per_step,
+the milliseconds one timed step took.  A plain run does only that: set up,
+W warm-up steps, K timed steps, the line.  --dump-outputs DIR then writes what
+the last timed step left (dump_outputs below) as DIR/<name>.npy; the inputs
+are seeded, so two builds can be compared output for output.  --full adds to
+the line what takes runs of its own: `roofline` for the dominant kernel (the
+3x3 implicit-GEMM conv, its launches of one more eager step replayed between
+HIP events after the timed region), `step` (the step's fraction of the matrix
+peak), `cpu_baseline` (the oracle's CPU restatement of the same step on a
+bounded sample, host threads stated) and `pck` (the recorded real-data runs).
 """
 import argparse
 import json
@@ -417,6 +421,31 @@ def cpu_baseline(steps=1, B=32):
                       % (B, steps, dt)}
 
 
+DUMP_SAMPLE = 1 << 20     # elements kept of each network's flat parameter / gradient vector
+
+
+def dump_outputs(out_dir, records, models, emas):
+    """What a caller of the timed path holds after its last step, as float32 /
+    float64 .npy files (~24 MB): train()'s return value (the loss records
+    averaged over the timed steps), and a fixed, seeded sample of DUMP_SAMPLE
+    elements of each student's parameters and last-step gradients and of each
+    EMA teacher's parameters (the vectors themselves are ~4 x 27 MB per kind)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    pec, mtc, epc, fdc = records
+    np.save(os.path.join(out_dir, "loss_records.npy"),
+            np.array(list(pec) + list(mtc) + list(epc) + [fdc], dtype=np.float64))
+    g = torch.Generator().manual_seed(1388)
+    for kind, nets in (("student", models), ("teacher", emas)):
+        for i, m in enumerate(nets):
+            flat = m.flat_params.detach().reshape(-1)
+            idx = torch.randperm(flat.numel(), generator=g)[:DUMP_SAMPLE].sort().values.to(flat.device)
+            np.save(os.path.join(out_dir, "%s%d_params.npy" % (kind, i)), flat[idx].float().cpu().numpy())
+            if kind == "student":
+                grads = m.flat_grads.detach().reshape(-1)
+                np.save(os.path.join(out_dir, "%s%d_grads.npy" % (kind, i)), grads[idx].float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -424,7 +453,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=None)
     ap.add_argument("--config", default="mt_ubpl", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and report the roofline kernel, the step's peak fraction, the CPU "
+                         "baseline and the recorded PCK runs (a plain run times the steps only)")
     a = ap.parse_args()
     cfg = CONFIGS[a.config]
     headline = a.config == "mt_ubpl"
@@ -483,17 +517,21 @@ def main():
     torch.cuda.synchronize()
     torch.cuda._sleep(1)          # window marker for tools/prof_summary.py (a ~1-cycle spin_kernel)
     t0 = time.perf_counter()
-    train(timed, models, emas, optims, args, verbose=False)
+    records = train(timed, models, emas, optims, args, verbose=False)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     torch.cuda._sleep(1)          # end marker: the kernels between the two markers are the timed steps'
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, records, models, emas)
     # roofline kernel: its launches from one more (eager, untimed) step, replayed
     # back to back between HIP events (standalone duration; see roofline())
     args.batch = B
-    roof = roofline(Kn, _lib, T, models, emas, optims, args, timed[0], dt / a.steps * 1e3, a.config, train)
+    roof = None
+    if a.full:
+        roof = roofline(Kn, _lib, T, models, emas, optims, args, timed[0], dt / a.steps * 1e3, a.config, train)
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -501,7 +539,7 @@ def main():
     images = world * B * a.steps
     if rank == 0:
         cpu = None
-        if not a.no_cpu_baseline and world == 1 and headline:
+        if a.full and not a.no_cpu_baseline and world == 1 and headline:
             cpu = cpu_baseline()
         line = {
             "metric": METRIC if headline else "images/sec training step (%s)" % cfg["desc"],
@@ -517,9 +555,10 @@ def main():
                        "per_gpu_batch": B, "input": "%dx%dx3" % (res, res),
                        "heatmap": "%dx%dx%d" % (K, res // 4, res // 4), "parallelism": "dp%d" % world,
                        "baseline_config": cfg["desc"]},
-            "roofline": roof, "step": step_record(cfg, B, dt / a.steps * 1e3, Kn.conv_precision_name()),
-            "cpu_baseline": cpu, "pck": pck_record() if headline else None,
         }
+        if a.full:
+            line.update({"roofline": roof, "step": step_record(cfg, B, dt / a.steps * 1e3, Kn.conv_precision_name()),
+                         "cpu_baseline": cpu, "pck": pck_record() if headline else None})
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -1,7 +1,7 @@
 """ORACLE — CPU restatement of the reference hot path.
 
 TEST INFRASTRUCTURE ONLY.  Nothing in the product (ubpl-poseestimation_amd/)
-imports this package; only tests/, __graft_entry__.smoke() and bench.py's
+imports this package; only tests/, __graft_entry__.smoke() and bench.py --full's
 cpu_baseline leg may, and only as the checker / the timed CPU baseline.
 
 Every function cites the reference file:line it restates (paths relative to

@@ -306,7 +306,8 @@ def gen_hourglass(R):
         preds = res if cfg["mode"] == "default" else res[0]
         out[cname + "/eval_preds_sum"] = np.array([preds.double().sum().item(), (preds.double() ** 2).sum().item()])
         out[cname + "/eval_preds"] = preds.numpy()[:, :, :, ::cfg["sub"], ::cfg["sub"]].copy()
-    np.savez_compressed(os.path.join(HERE, "hourglass.npz"), **out)
+    for name in seeds.HG_FILES:
+        np.savez_compressed(os.path.join(HERE, name), **{k: v for k, v in out.items() if seeds.hg_file(k) == name})
     with open(os.path.join(HERE, "hourglass_meta.json"), "w") as f:
         json.dump(meta, f)
 

@@ -5,6 +5,7 @@ inputs these functions build; the tests rebuild the same inputs from the same
 seeds (torch CPU Generator / numpy RandomState are deterministic for a fixed
 torch/numpy build, and the GPU box runs the same image).
 """
+import os
 import types
 
 import numpy as np
@@ -284,6 +285,25 @@ def hg_cases():
         # BASELINE.json configs[4]: 8 stacks at 384x384 input / 96x96 heatmaps
         "hg8_384": dict(K=16, S=8, mode="AvgPool", seed=11, B=2, res=384, sub=4, iseed=504),
     }
+
+
+# the H1 records, filed so that every committed file stays under 1 MiB
+HG_FILES = ("hourglass.npz", "hourglass_hg8_384.npz", "hourglass_hg8_384_eval.npz")
+
+
+def hg_file(key):
+    if not key.startswith("hg8_384/"):
+        return HG_FILES[0]
+    return HG_FILES[2] if key.startswith("hg8_384/eval_") else HG_FILES[1]
+
+
+def hg_golden(golden_dir):
+    """All H1 records ("<case>/<name>" -> array) from the HG_FILES."""
+    out = {}
+    for name in HG_FILES:
+        with np.load(os.path.join(golden_dir, name)) as z:
+            out.update({k: z[k] for k in z.files})
+    return out
 
 
 def hg_inputs(K, S, mode, seed, B, res, sub, iseed):

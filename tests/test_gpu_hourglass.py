@@ -89,7 +89,7 @@ def _our_grads(model):
                                   for c in seeds.hg_cases()])
 def test_hourglass_vs_golden(case):
     from ubpl_amd.hourglass import StackedHourglass
-    g = np.load(os.path.join(GD, "hourglass.npz"))
+    g = seeds.hg_golden(GD)
     meta = json.load(open(os.path.join(GD, "hourglass_meta.json")))[case]
     cfg = seeds.hg_cases()[case]
     torch.manual_seed(cfg["seed"])

@@ -8,10 +8,9 @@ bit-exact to the reference by test_oracle_golden), and the per-batch records
 are folded with the reference's AvgCounters weights (bs per keypoint entry,
 bs*k for the mean).  Accuracies are compared bit-exact, errors to 1e-6.
 
-Needs data/mouse_100_500_0.3.npz (tools/pack_mouse.py, run by
-__graft_entry__.build() in the build container; git-ignored, travels with the
-tree): a GPU run without it FAILS — the only real-data PCK check must not pass
-by being skipped.
+Reads the committed pack tests/golden/mouse_100_500_0.3/ (tools/pack_mouse.py:
+the split and its 600 grey images as .npz shards): a GPU run without it FAILS —
+the only real-data PCK check must not pass by being skipped.
 """
 import os
 import types
@@ -24,7 +23,7 @@ from oracle import decode as OD
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PACK = os.path.join(ROOT, "data", "mouse_100_500_0.3.npz")
+PACK = os.path.join(ROOT, "tests", "golden", "mouse_100_500_0.3")
 
 
 def _teachers(K=9, S=2):
@@ -40,8 +39,8 @@ def _teachers(K=9, S=2):
 
 
 def _require_pack():
-    assert os.path.exists(PACK), ("Mouse pack %s missing: build it with tools/pack_mouse.py (or "
-                                  "__graft_entry__.build()) where the reference tree exists" % PACK)
+    assert os.path.exists(os.path.join(PACK, "meta.npz")), (
+        "Mouse pack %s missing: write it with tools/pack_mouse.py where the reference tree exists" % PACK)
 
 
 def test_validate_on_mouse_split_matches_oracle():

@@ -155,7 +155,7 @@ def _stats(t):
 
 @pytest.mark.parametrize("case", list(seeds.hg_cases().keys()))
 def test_hourglass(case):
-    g = _npz("hourglass.npz")
+    g = seeds.hg_golden(GD)
     meta = json.load(open(os.path.join(GD, "hourglass_meta.json")))[case]
     cfg = seeds.hg_cases()[case]
     torch.manual_seed(cfg["seed"])

@@ -6,10 +6,10 @@
 #   tools/gpu.sh STEP [STEP ...]      with the steps, in the order given:
 #     smoke                 __graft_entry__.smoke()
 #     tests                 pytest -m gpu over $TESTS (default: tests), -k "$K" when set
-#     bench:<cfg>[:ENV=V,...]  python bench.py --config <cfg> (head = mt_ubpl, hb = mt_ubpl_hg2_256_bf16,
+#     bench:<cfg>[:ENV=V,...]  python bench.py --full --config <cfg> (head = mt_ubpl, hb = mt_ubpl_hg2_256_bf16,
 #                           c3 = dualpose_hg4, c4 = mt_ubpl_hg8_384, c5 = mt_ubpl_hg8_384_bf16);
 #                           $STEPS timed steps (20), $WARM warm-up (3), the CPU baseline only with CPU=1
-#     prof:<cfg>[:ENV=V,...]   rocprofv3 --kernel-trace --stats of a 3-step bench run, then
+#     prof:<cfg>[:ENV=V,...]   rocprofv3 --kernel-trace --stats of a 3-step bench --full run, then
 #                           tools/prof_summary.py over its timed window -> gpurun_out/prof_<cfg>.txt
 #                           (labelled with the profiled/benched ms ratio when bench:<cfg> ran first)
 #     pmc:bench             FETCH_SIZE / WRITE_SIZE passes over the bench (eager step) ->
@@ -46,7 +46,7 @@ for step in "$@"; do
     bench)
       c=$(cfg $name); [ $name = eager ] && extra="UBPL_STEP_GRAPH=0${extra:+,$extra}"
       tag=$name${extra:+_$(echo $extra | tr ',=/' '___')}
-      env $(envs "$extra") timeout -k 10 ${BENCH_TIMEOUT:-500} python bench.py --config $c --steps ${STEPS:-20} \
+      env $(envs "$extra") timeout -k 10 ${BENCH_TIMEOUT:-500} python bench.py --full --config $c --steps ${STEPS:-20} \
           --warmup ${WARM:-3} $([ "$CPU" = 1 ] || echo --no-cpu-baseline) > gpurun_out/bench_$tag.json 2> gpurun_out/bench_$tag.err
       rc=$?; [ $rc -ne 0 ] && { tail -5 gpurun_out/bench_$tag.err; stop bench $rc; }
       python -c "import json;d=json.load(open('gpurun_out/bench_$tag.json'));r=d['roofline'] or {};print('bench $tag:', d['value'], 'img/s', d['ms_per_step'], 'ms; roofline', r.get('avg_launch_us'), 'us frac', r.get('frac'), '; cpu', (d['cpu_baseline'] or {}).get('value'))" ;;
@@ -54,7 +54,7 @@ for step in "$@"; do
       c=$(cfg $name); tag=$name${extra:+_$(echo $extra | tr ',=/' '___')}
       rm -rf gpurun_out/prof_$tag; mkdir -p gpurun_out/prof_$tag
       env $(envs "$extra") timeout -k 10 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_$tag -o run \
-          --output-format csv -- python3 bench.py --config $c --steps 3 --warmup 2 --no-cpu-baseline \
+          --output-format csv -- python3 bench.py --full --config $c --steps 3 --warmup 2 --no-cpu-baseline \
           > gpurun_out/prof_$tag.json 2> gpurun_out/prof_$tag.err
       rc=$?; [ $rc -ne 0 ] && { tail -5 gpurun_out/prof_$tag.err; stop prof $rc; }
       tr=$(find gpurun_out/prof_$tag -name "*kernel_trace.csv" | head -1)
@@ -67,11 +67,11 @@ for step in "$@"; do
         for c in FETCH_SIZE WRITE_SIZE; do
           n=$(echo $c | cut -d_ -f1 | tr A-Z a-z)
           UBPL_STEP_GRAPH=0 timeout -k 10 600 rocprofv3 --pmc $c -d $OUT -o $n --output-format csv -- \
-              python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline > $OUT/$n.log 2>&1
+              python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $OUT/$n.log 2>&1
           rc=$?; echo "pmc $n rc=$rc"; [ $rc -ne 0 ] && stop pmc $rc
         done
         python3 tools/pmc_roofline.py $OUT gpurun_out/pmc_roofline_${PMC_KIND:-psah2}.json \
-            "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over bench.py --steps 2 --warmup 1 (eager step; tools/gpu.sh pmc:bench)" ${PMC_KIND:-psah2}
+            "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over bench.py --full --steps 2 --warmup 1 (eager step; tools/gpu.sh pmc:bench)" ${PMC_KIND:-psah2}
         rm -f $OUT/*.csv
       else
         # pmc:<script.py>[:ENV=V,...]: the script's environment (the program after -- stays python3)
@@ -91,7 +91,7 @@ for step in "$@"; do
       IFS='|' read -ra settings <<< "$arg"
       for r in $(seq 1 ${AB_ROUNDS:-2}); do
         for e in "${settings[@]}"; do
-          env $(envs "$e") timeout -k 10 400 python bench.py --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline \
+          env $(envs "$e") timeout -k 10 400 python bench.py --full --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline \
               > gpurun_out/ab.json 2> gpurun_out/ab.err || { rc=$?; tail -3 gpurun_out/ab.err; stop ab $rc; }
           python -c "import json; d=json.load(open('gpurun_out/ab.json')); print('ab [$e] r$r', d['value'], d['ms_per_step'], (d['roofline'] or {}).get('avg_launch_us'))"
         done

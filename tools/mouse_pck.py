@@ -8,7 +8,7 @@ the fused train step, HIP decode + PCK.
 
     python tools/mouse_pck.py [--epochs 100] [--model HG2] [--out profiles/r02_mouse_pck.json]
 
-Needs data/mouse_100_500_0.3.npz (tools/pack_mouse.py).
+Reads tests/golden/mouse_100_500_0.3/ (tools/pack_mouse.py).
 """
 import argparse
 import json

@@ -1,4 +1,4 @@
-"""From a rocprofv3 kernel trace of `bench.py`: the roofline kernel's average
+"""From a rocprofv3 kernel trace of `bench.py --full`: the roofline kernel's average
 duration in situ (the warm-up + timed + recording steps, networks overlapping)
 and in the back-to-back replays bench.py times with HIP events (the last
 (1 + reps) * launches_per_step launches of that kernel).

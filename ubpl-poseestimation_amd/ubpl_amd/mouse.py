@@ -15,8 +15,10 @@ paths remapped to a local image directory.  Reference quirks kept:
 * validation centre = [int(w/2), int(h/2)], scale = inpRes/200 as float32
   (datasets/dataset.py:33-35, utils/process.py:218-221).
 
-GPU boxes do not have the reference tree: tools/pack_mouse.py writes the split
-and its 600 images into one .npz (`write_pack`), which `from_pack` reads.
+Machines without the reference tree read the pack instead: the split and its
+600 images as small .npz shards under tests/golden/mouse_100_500_0.3/
+(tools/pack_mouse.py -> `write_pack`; `from_pack` reads it).  The images are
+grey (R == G == B in every PNG of the split), so a shard stores one channel.
 """
 import json
 import os
@@ -24,9 +26,10 @@ import os
 import numpy as np
 import torch
 
-PACK_NAME = "mouse_100_500_0.3.npz"
-DEFAULT_PACK = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "data",
-                            PACK_NAME)
+PACK_NAME = "mouse_100_500_0.3"
+DEFAULT_PACK = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "tests",
+                            "golden", PACK_NAME)
+SHARD = 20          # images per shard: every committed file stays well under 1 MiB
 
 
 def _bgr(path):
@@ -66,6 +69,8 @@ class MouseData:
     def from_pack(cls, path=DEFAULT_PACK):
         if not os.path.exists(path):
             raise FileNotFoundError("%s missing: run tools/pack_mouse.py in a tree with the reference data" % path)
+        if os.path.isdir(path):
+            return cls(pack=_read_shards(path))
         with np.load(path, allow_pickle=False) as z:
             pack = {k: z[k] for k in z.files}
         return cls(pack=pack)
@@ -93,11 +98,23 @@ class MouseData:
 
     # -- pack -------------------------------------------------------------
     def write_pack(self, path, trainCount, validCount, labelRatio):
+        """One .npz (path ends in .npz), or a directory of shards: meta.npz and
+        <split>_imgs_<nn>.npz with SHARD grey images each."""
         semi, valid, lab, unlab, lidx, uidx, means, stds = self.getSemiData(trainCount, validCount, labelRatio)
+        imgs = {"train_imgs": np.stack([_bgr(it["imagePath"]) for it in semi]),
+                "valid_imgs": np.stack([_bgr(it["imagePath"]) for it in valid])}
+        if path.endswith(".npz"):
+            meta = path
+        else:
+            os.makedirs(path, exist_ok=True)
+            meta = os.path.join(path, "meta.npz")
+            for name, x in imgs.items():
+                assert (x[..., 0] == x[..., 1]).all() and (x[..., 1] == x[..., 2]).all(), "not grey: " + name
+                for n, s in enumerate(range(0, len(x), SHARD)):
+                    np.savez_compressed(os.path.join(path, "%s_%02d.npz" % (name, n)), grey=x[s:s + SHARD, :, :, 0])
+            imgs = {}
         np.savez_compressed(
-            path,
-            train_imgs=np.stack([_bgr(it["imagePath"]) for it in semi]),
-            valid_imgs=np.stack([_bgr(it["imagePath"]) for it in valid]),
+            meta, **imgs,
             train_kps=np.array([it["kps"] for it in semi], np.float32),
             train_kps_test=np.array([it["kps_test"] for it in semi], np.float32),
             train_islabeled=np.array([it["islabeled"] for it in semi], np.int64),
@@ -131,6 +148,21 @@ class MouseData:
             return self._pack[split + "_imgs"]
         semi, valid = self._split(100, 500, 0.3)[:2]
         return np.stack([_bgr(it["imagePath"]) for it in (semi if split == "train" else valid)])
+
+
+def _read_shards(path):
+    """The pack dict from a shard directory (see MouseData.write_pack)."""
+    with np.load(os.path.join(path, "meta.npz"), allow_pickle=False) as z:
+        pack = {k: z[k] for k in z.files}
+    for name, count in (("train_imgs", len(pack["train_ids"])), ("valid_imgs", len(pack["valid_ids"]))):
+        parts = []
+        for n in range((count + SHARD - 1) // SHARD):
+            with np.load(os.path.join(path, "%s_%02d.npz" % (name, n)), allow_pickle=False) as z:
+                parts.append(z["grey"])
+        grey = np.concatenate(parts)
+        assert len(grey) == count, (name, len(grey), count)
+        pack[name] = np.ascontiguousarray(np.repeat(grey[..., None], 3, axis=3))
+    return pack
 
 
 def to_device_images(imgs_bgr, means, device):
