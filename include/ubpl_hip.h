@@ -217,7 +217,8 @@ int ubpl_wgrad_slab_reduce(const float* slab, int splits, int Cout, int Cin, int
 /*@ src:f32[?] dst:f32[?] table:i64[nseg*5] */
 int ubpl_conv_weights_relayout(const float* src, float* dst, const int64_t* table, int nseg, int mode, void* stream);
 
-/* Split MFMA path of the same Conv (conv_split.hip): every f32 operand carried
+/* Split MFMA path of the same Conv (split_common.h and the conv_*split*, conv_psa*,
+ * conv1x1_sol files): every f32 operand carried
  * as npieces 16-bit pieces, the piece products with pa + pb < npieces summed by
  * the 32x32x16 MFMA in f32: npieces 3 = three bf16 pieces ("6xbf16", exact
  * operands, 6 products), 2 = two fp16 pieces of the operand times a power-of-two
@@ -319,8 +320,10 @@ int ubpl_stem_weight_s2d_split(const float* w, int Cout, int C, int KS, int npie
  * ubpl_conv_weights_split (KS = 1); npieces 3 = 6xbf16, 2 = 2xfp16 (no epilogue
  * partials), 1 = bf16 operands (one plane; no epilogue partials).  Cin % 16 == 0, Cout % 16 == 0, P % 4 == 0.
  * stat_part (nullable): BatchNorm partials of y (ubpl_bn_partials layout).
- * _preferred: 1 when the shape is supported and fills the chip. */
+ * _preferred: 1 when the shape is supported and fills the chip (a grid of at least
+ * one workgroup per CU); _preferred_min: ... and its grid has at least min_wgs workgroups. */
 int ubpl_conv1x1_split_load_preferred(int B, int Cin, int Cout, int P);
+int ubpl_conv1x1_split_load_preferred_min(int B, int Cin, int Cout, int P, int min_wgs);
 /*@ x:f32[(int64_t)B*Cin*P] wsplit:u16[(npieces-1)*wplane+(int64_t)Cout*Cin] bias:f32[Cout] pscale:f32[Cin] pshift:f32[Cin] res:f32[(int64_t)B*Cout*P] y:f32[(int64_t)B*Cout*P] stat_part:f32[ubpl_bn_partial_floats(Cout,(int64_t)B*P)] bn_x:f32[(int64_t)B*Cout*P] bn_coef:f32[3*Cout] bn_part:f32[ubpl_bn_partial_floats(Cout,(int64_t)B*P)] */
 int ubpl_conv1x1_forward_split_load(const float* x, int B, int Cin, int P, const uint16_t* wsplit, int64_t wplane,
                                     const float* bias, int Cout, const float* pscale, const float* pshift,

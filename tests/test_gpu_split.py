@@ -1,4 +1,4 @@
-"""Split MFMA convolutions (conv_split.hip) vs float64 references.
+"""Split MFMA convolutions (split_common.h and the split-path files beside it) vs float64 references.
 
 The exact-f32 MFMA path (conv.hip) is the yardstick: on the same inputs the
 3-piece bf16 path (npieces=3, "6xbf16", exact operands) and the 2-piece fp16
@@ -581,6 +581,33 @@ def test_conv1x1_split_load_16_channels(case, npieces):
     e32, esp = _rel(dx32, dxref), _rel(dx, dxref)
     print("sol16 dgrad %s: f32 %.2e split-load %.2e" % (case, e32, esp))
     assert esp <= 2 * e32 + 1e-8, (esp, e32)
+
+
+def test_conv1x1_split_load_planner_matches_old_python_formula():
+    """ubpl_conv1x1_split_load_preferred_min (the one planner of the split-on-load 1x1, host
+    calls only) against the formula kernels.conv1x1_split_load_ok(small=True) used to carry in
+    Python, which assumed a 256-CU part: the same answer inside the kernel's limits, 0 outside
+    them (the formula knew no 32-bit size limit)."""
+    from ubpl_amd import _lib
+    lib = _lib.lib()
+
+    def old(B, Cin, Cout, P, min_wgs):
+        N = B * P
+        if not (Cin % 16 == 0 and Cout % 16 == 0 and P % 4 == 0 and N >= 4):
+            return False
+        bm = 128 if Cout % 128 == 0 and ((N + 255) // 256) * (Cout // 128) >= 256 else 64
+        return ((N + 255) // 256) * ((Cout + bm - 1) // bm) >= min_wgs
+
+    shapes = [(32, 256, 128, 1024), (32, 128, 256, 4096), (32, 256, 256, 64), (2, 256, 16, 4096),
+              (2, 16, 256, 1024), (1, 128, 128, 16), (1, 64, 64, 4), (3, 256, 256, 16)]
+    for min_wgs in (32, 256):
+        for s in shapes:
+            got = lib.ubpl_conv1x1_split_load_preferred_min(*s, min_wgs)
+            print("sol planner %s min_wgs=%d: %d (old formula %d)" % (s, min_wgs, got, old(*s, min_wgs)))
+            assert got == int(old(*s, min_wgs)), (s, min_wgs)
+        big = (64, 256, 128, 65536)            # B*Cin*P*4 = 2^32: over the kernel's 32-bit offsets
+        assert old(*big, min_wgs) and lib.ubpl_conv1x1_split_load_preferred_min(*big, min_wgs) == 0
+        assert lib.ubpl_conv1x1_split_load_preferred_min(2, 24, 64, 64, min_wgs) == 0   # Cin % 16 != 0
 
 
 @pytest.mark.parametrize("case", [(2, 256, 128, 64, True), (2, 128, 256, 32, True), (3, 256, 256, 16, False),

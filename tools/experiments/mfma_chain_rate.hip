@@ -1,7 +1,7 @@
 // What MFMA rate does conv_psa_kernel's inner structure allow with no memory at
 // all?  Per "K step" each wave runs TM x TN tiles, each a chain of 6 dependent
 // v_mfma_f32_32x32x16_bf16 (C = the previous result, first from zero) followed by
-// the f32 add of the chunk into the accumulator (conv_split.hip mfma_split0 +
+// the f32 add of the chunk into the accumulator (split_common.h mfma_split0 +
 // acc += tmp), 256-thread workgroups, 2 per CU (the kernel's occupancy).
 //   mode 0: one temporary, tiles in sequence (what hipcc emits for conv_psa)
 //   mode 1: two tiles' chains interleaved (two temporaries)

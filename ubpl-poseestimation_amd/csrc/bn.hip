@@ -835,7 +835,7 @@ UBPL_API int ubpl_bn_apply(const float* x, int B, int C, int HW, const float* sc
 // Backward of y = [relu](bn(x)) given dz = dL/dy.  dgamma/dbeta are
 // ACCUMULATED (+=).  dx = add1 + add2 + dL/dx (add1/add2 nullable; dx may
 // alias dz, add1 or add2).  coef: scratch of 3*C floats.
-// dx of the BN backward written straight into the PSA layout (conv_split.hip
+// dx of the BN backward written straight into the PSA layout (conv_psa.hip
 // split_act_kernel's [B][C/16][H+2pad][W+2pad][16] bf16 planes, zero border):
 // one thread per padded pixel of one 16-channel group, like split_act.
 template <int NP>

@@ -139,7 +139,7 @@ __device__ __forceinline__ void seed_acc(ACC (&acc)[TM][TN], const float* bias, 
 // relative (two 11-bit significands), the piece products hi.hi + hi.lo + lo.hi exact
 // in f32: operands within a few f32 ulps with 3 MFMA products instead of 6.  fp16's exponent range is narrow
 // (normal from 2^-14, max 65504), so the callers pass values pre-scaled by a power
-// of two that puts them there (conv_split.hip: FP16_ACT_SCALE, fp16_wscale) and
+// of two that puts them there (the split-path files: FP16_ACT_SCALE, fp16_wscale) and
 // undo the scale exactly on the accumulators.
 constexpr float FP16_ACT_SCALE = 32.f;   // activations: |v| up to 2047 without overflow, full
                                          // precision from |v| >= 2^-7 (below: absolute error <= 2^-30)
@@ -175,7 +175,7 @@ __device__ __forceinline__ void split2(float a, float b, uint32_t (&o)[NP]) {
 }
 
 // 16 channel values of one pixel -> the NP bf16 planes of a PSA image row
-// (conv_split.hip split_act_kernel layout): 32 contiguous bytes per plane.
+// (conv_psa.hip split_act_kernel layout): 32 contiguous bytes per plane.
 template <int NP>
 __device__ __forceinline__ void store_psa_row(const float (&v)[16], uint16_t* d, int64_t plane, float sc = 1.f) {
     uint32_t pk[NP][8];

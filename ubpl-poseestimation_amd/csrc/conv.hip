@@ -320,7 +320,7 @@ __global__ void __launch_bounds__(NT, 4) conv_fwd_kernel(const float* __restrict
 // LDS-DMA (global_load_lds_dwordx4, 1 KB per wave instruction), no staging
 // registers.  The fused pre-activation relu(x*scale + shift) is applied to the
 // B fragment after its LDS read (2 VALU per 2 MFMAs).  3-stage ring with
-// counted vmcnt and a raw s_barrier, as conv_split.hip's conv_psa_kernel.
+// counted vmcnt and a raw s_barrier, as conv_psa.hip's conv_psa_kernel.
 // Fragment reads are ds_read_b32 of 32 consecutive floats per half-wave
 // (conflict-free, no swizzle).
 typedef __attribute__((address_space(3))) void* lds_ptr_t;

@@ -75,6 +75,7 @@ SIGNATURES = {
     "ubpl_stem_s2d_split": (I, [P, I, I, I, I, I, I, P, L, P]),
     "ubpl_stem_weight_s2d_split": (I, [P, I, I, I, I, P, L, P]),
     "ubpl_conv1x1_split_load_preferred": (I, [I, I, I, I]),
+    "ubpl_conv1x1_split_load_preferred_min": (I, [I, I, I, I, I]),
     "ubpl_conv1x1_forward_split_load": (I, [P, I, I, I, P, L, P, I, P, P, P, P, P, P, P, I, P, I, P]),
     "ubpl_maxpool2x2_forward": (I, [P, L, I, I, P, P]),
     "ubpl_maxpool2x2_backward": (I, [P, P, L, I, I, P, I, P]),

@@ -255,7 +255,7 @@ class StackedHourglass(nn.Module):
         """Conv arithmetic (kernels.CONV_PRECISIONS; None = $UBPL_CONV_PRECISION or the default):
         'f32'    every conv on the exact-f32 MFMA (conv.hip);
         '6xbf16' the 3x3 convs (forward and data gradient) on split-bf16 MFMA with
-                 3 bf16 pieces per operand over pre-split activations (conv_split.hip
+                 3 bf16 pieces per operand over pre-split activations (conv_psa.hip, conv_psah.hip
                  PSA path, error at the f32 path's level), the 1x1 convs whose
                  planes fill the chip on the same arithmetic with the activations
                  split while they are staged, the rest f32;
@@ -638,21 +638,19 @@ class _Exec:
                 return Kn.conv1x1_forward_split_load(x, ws, b, ps, ph, res=res, out=out, stat_part=part), part
             if ws.npieces in (2, 3):
                 ws = None                                # small plane: the f32 1x1 kernel (bf16: the PSA kernel)
-        if ws is not None:
-            if ws.npieces in (1, 2, 3):
-                part = mkpart() if ws.npieces != 2 else None
-                keep = self.do_save and ws.shape[1] == 9
-                if ws.npieces == 2 and keep and self.m.bwd3_pieces == 3:
-                    # 2xfp16 forward, 6xbf16 gradients: the conv's fp16 image and, from the same
-                    # read, the 6xbf16 one its weight gradient takes
-                    xs, xs3 = Kn.split_activation(x, 2, 1, ps, ph, with3=True)
-                    self.saved_split[name] = xs3
-                else:
-                    xs = Kn.split_activation(x, ws.npieces, (ws.shape[1] == 9) * 1, ps, ph)
-                    if keep:
-                        self.saved_split[name] = xs      # the 3x3 weight gradient's B operand
-                return Kn.conv2d_forward_psa(xs, ws, b, res=res, out=out, stat_part=part), part
-            return Kn.conv2d_forward_split(x, ws, b, ps, ph, res=res, out=out), None
+        if ws is not None:                               # (npieces 1, 2 or 3: every precision SW knows)
+            part = mkpart() if ws.npieces != 2 else None
+            keep = self.do_save and ws.shape[1] == 9
+            if ws.npieces == 2 and keep and self.m.bwd3_pieces == 3:
+                # 2xfp16 forward, 6xbf16 gradients: the conv's fp16 image and, from the same
+                # read, the 6xbf16 one its weight gradient takes
+                xs, xs3 = Kn.split_activation(x, 2, 1, ps, ph, with3=True)
+                self.saved_split[name] = xs3
+            else:
+                xs = Kn.split_activation(x, ws.npieces, (ws.shape[1] == 9) * 1, ps, ph)
+                if keep:
+                    self.saved_split[name] = xs      # the 3x3 weight gradient's B operand
+            return Kn.conv2d_forward_psa(xs, ws, b, res=res, out=out, stat_part=part), part
         if w.shape[2] == 1 and stride == 1 and Kn.conv1x1_kmajor_ok(x, w.shape[0]):
             part = mkpart()
             return Kn.conv1x1_forward_kmajor(x, self.m.W(1, name + ".weight"), b, ps, ph, res=res, out=out,
@@ -785,11 +783,9 @@ class _Exec:
                 ws = None
         if bnb is not None:
             return self.dgrad(name, dy, res=res, out=out), None
-        if ws is not None:
-            if ws.npieces in (1, 3):
-                ys = Kn.split_activation(dy, ws.npieces, (ws.shape[1] == 9) * 1)
-                return Kn.conv2d_forward_psa(ys, ws, None, res=res, out=out)
-            return Kn.conv2d_forward_split(dy, ws, None, res=res, out=out)
+        if ws is not None:   # (npieces 1 or 3: the 2xfp16 3x3 data gradients run in residual_bwd)
+            ys = Kn.split_activation(dy, ws.npieces, (ws.shape[1] == 9) * 1)
+            return Kn.conv2d_forward_psa(ys, ws, None, res=res, out=out)
         w = self.m.P(name + ".weight")
         if w.shape[2] == 1 and Kn.conv1x1_kmajor_ok(dy, w.shape[1]):
             return Kn.conv1x1_forward_kmajor(dy, w, None, res=res, out=out)     # [Cout][Cin] = k-major

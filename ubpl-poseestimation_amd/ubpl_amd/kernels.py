@@ -391,7 +391,7 @@ def conv_weights_relayout(src, dst, table, mode):
 # split-bf16 MFMA with 3 bf16 pieces per f32 operand (6 piece products, f32
 # accumulation: exact operands); "2xfp16" = the forward convs (students' and
 # teachers') with 2 fp16 pieces per operand of the power-of-two-scaled value (3
-# piece products on the fp16 MFMA, operands to 2^-22: conv_split.hip / common.h
+# piece products on the fp16 MFMA, operands to 2^-22: split_common.h / common.h
 # split2), the backward (data and weight gradients, whose operands have no
 # known range) on 6xbf16; "bf16" = one piece, i.e. both operands rounded to bf16
 # (RNE) with f32 accumulation — the throughput precision of BASELINE config 5
@@ -422,7 +422,7 @@ def conv_precision_pieces(name=None):
 
 
 class SplitWeights:
-    """One conv's weights as `npieces` bf16 planes (conv_split.hip): a view into
+    """One conv's weights as `npieces` bf16 planes (conv_weights_split.hip): a view into
     a shared buffer `buf` (int16, planes `plane` elements apart) at element
     offset `off`; shape = (rows, KS*KS, cols) of the GEMM A operand."""
 
@@ -471,7 +471,7 @@ def conv2d_forward_split(x, ws, bias, pscale=None, pshift=None, res=None, out=No
 
 
 class SplitAct:
-    """Pre-split activations (conv_split.hip PSA layout): `npieces` 16-bit planes of
+    """Pre-split activations (conv_psa.hip PSA layout): `npieces` 16-bit planes of
     [B][C/16][H+2pad][W+2pad][16] in an int16 buffer, planes `plane` elements apart
     (3: bf16 pieces; 2: fp16 pieces of v * 32, the 2xfp16 path; 1: bf16(v))."""
 
@@ -567,12 +567,7 @@ def conv1x1_split_load_ok(x, ws, small=False):
     if not ok:
         return False
     if small and _SOL_MINWG > 0 and ws.npieces in (2, 3):
-        Cout, P = ws.shape[0], H * W
-        N = B * P
-        if not (Cin % 16 == 0 and Cout % 16 == 0 and P % 4 == 0 and N >= 4):
-            return False
-        bm = 128 if Cout % 128 == 0 and ((N + 255) // 256) * (Cout // 128) >= 256 else 64
-        return ((N + 255) // 256) * ((Cout + bm - 1) // bm) >= _SOL_MINWG
+        return bool(_lib.lib().ubpl_conv1x1_split_load_preferred_min(B, Cin, ws.shape[0], H * W, _SOL_MINWG))
     return bool(_lib.lib().ubpl_conv1x1_split_load_preferred(B, Cin, ws.shape[0], H * W))
 
 
