@@ -83,6 +83,21 @@ int ubpl_fdl_cov_backward(const float* f1, const float* f2, const float* rowmask
 /*@ hm:f32[(int64_t)N*K*H*W] tinv:f64[N*6] raw:f32[N*K*2] preds:f32[N*K*2] scores:f32[N*K] */
 int ubpl_decode_heatmaps(const float* hm, int N, int K, int H, int W, const double* tinv, float* raw, float* preds,
                          float* scores, void* stream);
+/* Flip test fused into the decode: the heatmaps of the mirrored image flipped
+ * back (utils/augment.py:239-252 fliplr_back / fliplr_back_tensor), their
+ * left/right joints swapped (utils/udaap/transforms.py:20-57 flip_back),
+ * averaged with the image's own and decoded as ubpl_decode_heatmaps does, in
+ * one read of both sets.  Map (n, k) of hm starts at hm + n*sb + k*H*W (sb: the
+ * batch stride in floats, so the last stack of a [B,S,K,H,W] output is decoded
+ * in place); hm_flip likewise.  merged[n,k,y,x] = (hm[n,k,y,x] +
+ * hm_flip[n,perm[k],y,W-1-x]) * 0.5f; perm int32 [K], null = identity (the
+ * reference's own convention: kps_fliplr, utils/process.py:239-242, mirrors x
+ * and swaps nothing), entries in [0, K); hm_flip null: merged = hm (a strided
+ * plain decode).  merged [N,K,H,W] contiguous, raw, preds, scores, tinv nullable. */
+/*@ hm:f32[(N-1)*sb+(int64_t)K*H*W] hm_flip:f32[(N-1)*sb+(int64_t)K*H*W] perm:i32[K] tinv:f64[N*6] merged:f32[(int64_t)N*K*H*W] raw:f32[N*K*2] preds:f32[N*K*2] scores:f32[N*K] */
+int ubpl_decode_heatmaps_flip(const float* hm, const float* hm_flip, int64_t sb, int N, int K, int H, int W,
+                              const int* perm, const double* tinv, float* merged, float* raw, float* preds,
+                              float* scores, void* stream);
 /* EvaluationUtils.acc_pck (utils/evaluation.py:91-139).  errs/accs [K+1];
  * hits/valid [K] int32 (nullable) for cross-rank aggregation. */
 /*@ preds:f32[N*K*2] gts:f32[N*K*3] errs:f32[K+1] accs:f32[K+1] hits:i32[K] valid:i32[K] */
@@ -128,6 +143,17 @@ int ubpl_bn_forward_stats(const float* x, int B, int C, int HW, const float* gam
 /*@ gamma:f32[C] beta:f32[C] rmean:f32[C] rvar:f32[C] scale:f32[C] shift:f32[C] */
 int ubpl_bn_eval_coeffs(const float* gamma, const float* beta, const float* rmean, const float* rvar, float eps,
                         int C, float* scale, float* shift, void* stream);
+/* Eval-mode coefficients of EVERY BatchNorm of a network in one launch (the
+ * frozen inference path: models/base/layers.py:41,57-61 in eval mode, once per
+ * weight snapshot instead of once per BN per forward).  table int64 [nbn][6] =
+ * (gamma_off, beta_off, rmean_off, rvar_off, coef_off, C): offsets in floats
+ * into params (gamma, beta), stats (rmean, rvar) and coef; row i writes scale
+ * at coef + coef_off and shift at coef + coef_off + C, bit-identical to
+ * ubpl_bn_eval_coeffs per BN.  The extents below are the least any table needs
+ * (C >= 1); the caller owns the table's offsets. */
+/*@ params:f32[2*nbn] stats:f32[2*nbn] table:i64[6*nbn] coef:f32[2*nbn] */
+int ubpl_bn_eval_coeffs_table(const float* params, const float* stats, const int64_t* table, int nbn, float eps,
+                              float* coef, void* stream);
 /*@ x:f32[(int64_t)B*C*HW] scale:f32[C] shift:f32[C] y:f32[(int64_t)B*C*HW] */
 int ubpl_bn_apply(const float* x, int B, int C, int HW, const float* scale, const float* shift, int relu, float* y,
                   void* stream);
@@ -349,6 +375,10 @@ int ubpl_upsample2x_add_backward(const float* dout, int64_t planes, int H, int W
                                  void* stream);
 /*@ a:f32[n] b:f32[n] out:f32[n] */
 int ubpl_add(const float* a, const float* b, int64_t n, float* out, void* stream);
+/* ProcessUtils.image_fliplr (utils/process.py:200-207) on device planes:
+ * y[p,r,c] = x[p,r,W-1-c], y != x, any W >= 1, 4-byte alignment. */
+/*@ x:f32[planes*H*W] y:f32[planes*H*W] */
+int ubpl_fliplr(const float* x, int64_t planes, int H, int W, float* y, void* stream);
 /* The same forwards + BatchNorm partials of the output for the BN that
  * consumes it (ubpl_bn_partials layout); output planes of a multiple of 64 pixels. */
 /*@ x:f32[(int64_t)B*C*H*W] y:f32[(int64_t)B*C*(H/2)*(W/2)] part:f32[ubpl_bn_partial_floats(C,(int64_t)B*(H/2)*(W/2))] */

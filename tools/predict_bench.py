@@ -1,0 +1,116 @@
+"""Inference latency: today's eager path against the Predictor's graph replay.
+
+For one HG<n> teacher (default HG2, K=16, 256x256, the flagship network) and each
+batch size (default 1, 8, 32), three ways of getting keypoints from images on the
+device:
+
+  (a) eager    model.eval()(x), then Kn.decode_heatmaps of the contiguous copy of the
+               last stack — what train.validate does per batch;
+  (b) replay   Predictor.predict(x, center, scale): copy into the static inputs,
+               graph replay, clone of the outputs;
+  (c) flip     the same with flip_test=True (a [2B] batch inside).
+
+Timing: every variant warmed up (graphs captured) first; then REPEATS rounds in
+which (a), (b), (c) alternate, each timed over enough calls for >= --window seconds
+with a host clock around work that ends in a device synchronise.  Per variant the
+median of the rounds is reported, with the spread (max - min) / median across them.
+(b) and (a) must agree bit for bit before anything is timed.  One JSON line on
+stdout (--out: also written to a file).  No GPU, no number: there is no CPU fallback.
+
+    python tools/predict_bench.py [--stacks 2] [--res 256] [--batches 1,8,32] [--out FILE]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "ubpl-poseestimation_amd"))
+
+
+def timed(fn, calls):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(calls):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / calls * 1e3
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--stacks", type=int, default=2)
+    ap.add_argument("--k", type=int, default=16)
+    ap.add_argument("--res", type=int, default=256)
+    ap.add_argument("--batches", default="1,8,32")
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--window", type=float, default=0.25, help="seconds of work per variant per round")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+
+    from ubpl_amd import Predictor, _lib, kernels as Kn
+    from ubpl_amd.hourglass import StackedHourglass
+    from ubpl_amd.process import inverse_transforms
+    _lib.require_gpu()
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    torch.manual_seed(0)
+    model = StackedHourglass(a.k, a.stacks, "AvgPool")
+    gen = torch.Generator().manual_seed(1)
+    with torch.no_grad():
+        for _ in range(2):                       # running statistics off their initial values
+            model((torch.rand(4, 3, a.res, a.res, generator=gen) - 0.5).to(dev))
+    model.eval()
+    plain = Predictor(model)
+    flip = Predictor(model, flip_test=True)
+    rows = []
+    for B in [int(b) for b in a.batches.split(",")]:
+        x = (torch.rand(B, 3, a.res, a.res, generator=gen) - 0.5).to(dev)
+        center = torch.full((B, 2), a.res / 2.0)
+        scale = torch.full((B,), a.res / 200.0)
+        tinv = inverse_transforms(center, scale, [a.res // 4, a.res // 4]).to(dev)
+
+        def eager():
+            with torch.no_grad():
+                o = model(x)[0]
+                return Kn.decode_heatmaps(o[:, -1].contiguous(), tinv)
+
+        variants = {"eager": eager, "replay": lambda: plain.predict(x, center, scale),
+                    "flip": lambda: flip.predict(x, center, scale)}
+        ref = eager()
+        got = plain.predict(x, center, scale)
+        if not (torch.equal(ref[0], got["raw"][0]) and torch.equal(ref[1], got["preds"][0])
+                and torch.equal(ref[2], got["scores"][0])):
+            raise SystemExit("predict_bench: the replay and the eager path disagree at B=%d" % B)
+        calls = {}
+        for name, fn in variants.items():        # warm-up, and the call count of a round's window
+            timed(fn, 3)
+            calls[name] = max(3, int(a.window * 1e3 / timed(fn, 5)) + 1)
+        ms = {name: [] for name in variants}
+        for _ in range(a.repeats):
+            for name, fn in variants.items():
+                ms[name].append(timed(fn, calls[name]))
+        row = {"B": B}
+        for name, v in ms.items():
+            v = sorted(v)
+            med = v[len(v) // 2]
+            row[name + "_ms"] = round(med, 4)
+            row[name + "_spread"] = round((v[-1] - v[0]) / med, 4)
+            row[name + "_seconds_timed"] = round(sum(v) * calls[name] / 1e3, 2)
+        row["replay_speedup"] = round(row["eager_ms"] / row["replay_ms"], 3)
+        row["flip_over_2x_replay"] = round(row["flip_ms"] / (2 * row["replay_ms"]), 3)
+        rows.append(row)
+    out = {"tool": "predict_bench", "model": "HG%d" % a.stacks, "k": a.k, "res": a.res,
+           "precision": Kn.conv_precision_name(), "repeats": a.repeats, "device": torch.cuda.get_device_name(0),
+           "rows": rows}
+    line = json.dumps(out)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
+if __name__ == "__main__":
+    main()

@@ -235,15 +235,39 @@ __global__ void __launch_bounds__(256) stats_kernel(const float* __restrict__ x,
     }
 }
 
+// Eval-mode scale / shift of one channel (one expression for both kernels below: the same rounding)
+__device__ __forceinline__ void eval_coeff(float gamma, float beta, float rmean, float rvar, float eps, float& scale,
+                                           float& shift) {
+    const float invstd = (float)(1.0 / sqrt((double)rvar + (double)eps));
+    const float sc = invstd * gamma;
+    scale = sc;
+    shift = beta - rmean * sc;
+}
+
 __global__ void eval_coeff_kernel(const float* __restrict__ gamma, const float* __restrict__ beta,
                                   const float* __restrict__ rmean, const float* __restrict__ rvar, float eps, int C,
                                   float* __restrict__ scale, float* __restrict__ shift) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
-    const float invstd = (float)(1.0 / sqrt((double)rvar[c] + (double)eps));
-    const float sc = invstd * gamma[c];
-    scale[c] = sc;
-    shift[c] = beta[c] - rmean[c] * sc;
+    eval_coeff(gamma[c], beta[c], rmean[c], rvar[c], eps, scale[c], shift[c]);
+}
+
+// The same for every BatchNorm of a network: one workgroup per row of `table`
+// (gamma_off, beta_off, rmean_off, rvar_off, coef_off, C), see ubpl_bn_eval_coeffs_table.
+__global__ void __launch_bounds__(256) eval_coeff_table_kernel(const float* __restrict__ params,
+                                                              const float* __restrict__ stats,
+                                                              const int64_t* __restrict__ table, float eps,
+                                                              float* __restrict__ coef) {
+    const int64_t* t = table + (int64_t)blockIdx.x * 6;
+    const float* gamma = params + t[0];
+    const float* beta = params + t[1];
+    const float* rmean = stats + t[2];
+    const float* rvar = stats + t[3];
+    const int C = (int)t[5];
+    float* scale = coef + t[4];
+    float* shift = scale + C;
+    for (int c = threadIdx.x; c < C; c += blockDim.x)
+        eval_coeff(gamma[c], beta[c], rmean[c], rvar[c], eps, scale[c], shift[c]);
 }
 
 __global__ void __launch_bounds__(256) apply_kernel(const float* __restrict__ x, const float* __restrict__ scale,
@@ -817,6 +841,16 @@ UBPL_API int ubpl_bn_eval_coeffs(const float* gamma, const float* beta, const fl
                                  float eps, int C, float* scale, float* shift, void* stream) {
     hipLaunchKernelGGL(eval_coeff_kernel, dim3(ubpl::cdiv(C, 64)), dim3(64), 0, (hipStream_t)stream, gamma, beta,
                        rmean, rvar, eps, C, scale, shift);
+    UBPL_LAUNCH_CHECK();
+    return 0;
+}
+
+UBPL_API int ubpl_bn_eval_coeffs_table(const float* params, const float* stats, const int64_t* table, int nbn,
+                                       float eps, float* coef, void* stream) {
+    if (nbn < 0) return (int)hipErrorInvalidValue;
+    if (nbn == 0) return 0;
+    hipLaunchKernelGGL(eval_coeff_table_kernel, dim3(nbn), dim3(256), 0, (hipStream_t)stream, params, stats, table,
+                       eps, coef);
     UBPL_LAUNCH_CHECK();
     return 0;
 }

@@ -13,6 +13,12 @@
 // through the host-computed float64 inverse transform (same entries as the
 // reference: float32 arithmetic for h = 200*scale, np.linalg.inv in f64) with
 // un-fused f64 multiply/add in np.dot's order, truncated toward zero, + 1.
+//
+// decode with the flip test (ubpl_decode_heatmaps_flip): the same decode of
+// (hm + flipped-back, pair-swapped hm_flip) / 2 — fliplr_back / flip_back
+// (utils/augment.py:239-252, utils/udaap/transforms.py:20-57) and the average
+// fused into the one read of both heatmap sets, which are addressed through a
+// batch stride (the last stack of a [B,S,K,H,W] network output, in place).
 #include "common.h"
 
 namespace {
@@ -24,24 +30,11 @@ __device__ __forceinline__ bool beats(float v, int i, float bv, int bi) {
     return v > bv || (v == bv && i < bi);
 }
 
-__global__ void __launch_bounds__(256) argmax_kernel(const float* __restrict__ hm, int maps, int H, int W,
-                                                    const double* __restrict__ tinv, int K,
-                                                    float* __restrict__ raw, float* __restrict__ preds,
-                                                    float* __restrict__ scores) {
-    const int lane = threadIdx.x & 63;
-    const int map = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (map >= maps) return;
-    const int HW = H * W;
-    const float* m = hm + (int64_t)map * HW;
-    float bv = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int i = lane; i < HW; i += 64) {
-        const float v = m[i];
-        if (beats(v, i, bv, bi)) {
-            bv = v;
-            bi = i;
-        }
-    }
+// The lanes' (value, first index) candidates of one map -> its decoded point,
+// written by lane 0 (the rules in the header comment above).
+__device__ __forceinline__ void finish_map(float bv, int bi, int lane, int map, int W, const double* __restrict__ tinv,
+                                           int K, float* __restrict__ raw, float* __restrict__ preds,
+                                           float* __restrict__ scores) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float ov = __shfl_xor(bv, o, 64);
@@ -68,6 +61,74 @@ __global__ void __launch_bounds__(256) argmax_kernel(const float* __restrict__ h
         preds[map * 2 + 0] = (float)((long long)rx + 1);  // astype(int) + 1 (:158)
         preds[map * 2 + 1] = (float)((long long)ry + 1);
     }
+}
+
+__global__ void __launch_bounds__(256) argmax_kernel(const float* __restrict__ hm, int maps, int H, int W,
+                                                    const double* __restrict__ tinv, int K,
+                                                    float* __restrict__ raw, float* __restrict__ preds,
+                                                    float* __restrict__ scores) {
+    const int lane = threadIdx.x & 63;
+    const int map = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (map >= maps) return;
+    const int HW = H * W;
+    const float* m = hm + (int64_t)map * HW;
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int i = lane; i < HW; i += 64) {
+        const float v = m[i];
+        if (beats(v, i, bv, bi)) {
+            bv = v;
+            bi = i;
+        }
+    }
+    finish_map(bv, bi, lane, map, W, tinv, K, raw, preds, scores);
+}
+
+// Flip test (ubpl_decode_heatmaps_flip): map (n, k) = (hm[n,k] + mirror(hm_flip[n,perm[k]])) / 2,
+// stored to `merged` (nullable) and decoded from the registers.  One wave per map, as above; a
+// wave's 64 consecutive pixels of a row read 64 consecutive floats of hm_flip's row in
+// descending order, so both loads stay contiguous.  FLIP false: hm alone (batch stride sb).
+template <bool FLIP>
+__global__ void __launch_bounds__(256) argmax_flip_kernel(const float* __restrict__ hm,
+                                                         const float* __restrict__ hm_flip, int64_t sb, int maps,
+                                                         int H, int W, const int* __restrict__ perm,
+                                                         const double* __restrict__ tinv, int K,
+                                                         float* __restrict__ merged, float* __restrict__ raw,
+                                                         float* __restrict__ preds, float* __restrict__ scores) {
+    const int lane = threadIdx.x & 63;
+    const int map = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (map >= maps) return;
+    const int HW = H * W;
+    const int n = map / K, k = map - n * K;
+    const float* a = hm + n * sb + (int64_t)k * HW;
+    const float* b = nullptr;
+    if (FLIP) {
+        int pk = perm != nullptr ? perm[k] : k;
+        if ((unsigned)pk >= (unsigned)K) pk = k;      // (a bad table must not read out of bounds)
+        b = hm_flip + n * sb + (int64_t)pk * HW;
+    }
+    float* mo = merged != nullptr ? merged + (int64_t)map * HW : nullptr;
+    // pixel i = lane + 64 t at (y, x), stepped without a division per element
+    const int dy = 64 / W, dx = 64 - dy * W;
+    int y = lane / W, x = lane - y * W;
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int i = lane; i < HW; i += 64) {
+        float v = a[i];
+        if (FLIP) v = (v + b[y * W + (W - 1 - x)]) * 0.5f;
+        if (mo != nullptr) mo[i] = v;
+        if (beats(v, i, bv, bi)) {
+            bv = v;
+            bi = i;
+        }
+        y += dy;
+        x += dx;
+        if (x >= W) {
+            x -= W;
+            y += 1;
+        }
+    }
+    finish_map(bv, bi, lane, map, W, tinv, K, raw, preds, scores);
 }
 
 // PCK (utils/evaluation.py:91-139).  One workgroup; thread per keypoint.
@@ -124,6 +185,25 @@ UBPL_API int ubpl_decode_heatmaps(const float* hm, int N, int K, int H, int W, c
     if (maps == 0) return 0;
     hipLaunchKernelGGL(argmax_kernel, dim3(ubpl::cdiv(maps, 4)), dim3(256), 0, (hipStream_t)stream, hm, maps, H, W,
                        tinv, K, raw, preds, scores);
+    UBPL_LAUNCH_CHECK();
+    return 0;
+}
+
+// Flip-test decode (see include/ubpl_hip.h): hm / hm_flip maps at n*sb + k*H*W.
+UBPL_API int ubpl_decode_heatmaps_flip(const float* hm, const float* hm_flip, int64_t sb, int N, int K, int H, int W,
+                                       const int* perm, const double* tinv, float* merged, float* raw, float* preds,
+                                       float* scores, void* stream) {
+    if (N < 0 || K < 1 || H < 1 || W < 1 || (int64_t)H * W > 0x7fffffff || (int64_t)N * K > 0x3fffffff ||
+        (N > 1 && sb < (int64_t)K * H * W) || (preds != nullptr && tinv == nullptr))
+        return (int)hipErrorInvalidValue;
+    const int maps = N * K;
+    if (maps == 0) return 0;
+    if (hm_flip != nullptr)
+        hipLaunchKernelGGL(argmax_flip_kernel<true>, dim3(ubpl::cdiv(maps, 4)), dim3(256), 0, (hipStream_t)stream, hm,
+                           hm_flip, sb, maps, H, W, perm, tinv, K, merged, raw, preds, scores);
+    else
+        hipLaunchKernelGGL(argmax_flip_kernel<false>, dim3(ubpl::cdiv(maps, 4)), dim3(256), 0, (hipStream_t)stream,
+                           hm, hm_flip, sb, maps, H, W, perm, tinv, K, merged, raw, preds, scores);
     UBPL_LAUNCH_CHECK();
     return 0;
 }

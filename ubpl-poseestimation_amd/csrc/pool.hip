@@ -194,7 +194,44 @@ __global__ void __launch_bounds__(256) add_kernel(const float* a, const float* b
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = a[i] + b[i];
 }
 
+// y[r, c] = x[r, W-1-c] over rows = planes*H rows (the flip test's mirrored image):
+// one output element per thread, or (VEC, W % 4 == 0, 16-B aligned) one float4 of the
+// output from the mirrored float4 of the row, its lanes reversed.
+template <bool VEC>
+__global__ void __launch_bounds__(256) fliplr_kernel(const float* __restrict__ x, int64_t rows, int W,
+                                                    float* __restrict__ y) {
+    const int Wv = VEC ? W >> 2 : W;
+    const int64_t total = rows * Wv;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        const int64_t r = i / Wv;
+        const int c = (int)(i - r * Wv);
+        const int64_t src = r * Wv + (Wv - 1 - c);
+        if (VEC) {
+            const float4 v = reinterpret_cast<const float4*>(x)[src];
+            reinterpret_cast<float4*>(y)[i] = make_float4(v.w, v.z, v.y, v.x);
+        } else {
+            y[i] = x[src];
+        }
+    }
+}
+
 }  // namespace
+
+UBPL_API int ubpl_fliplr(const float* x, int64_t planes, int H, int W, float* y, void* stream) {
+    if (planes < 0 || H < 0 || W < 0 || x == y) return (int)hipErrorInvalidValue;
+    const int64_t rows = planes * H;
+    if (rows == 0 || W == 0) return 0;
+    if ((W % 4) == 0 && ((((uintptr_t)x) | ((uintptr_t)y)) & 15) == 0) {
+        hipLaunchKernelGGL(fliplr_kernel<true>, dim3(grid_ew(rows * (W / 4))), dim3(256), 0, (hipStream_t)stream, x,
+                           rows, W, y);
+    } else {
+        hipLaunchKernelGGL(fliplr_kernel<false>, dim3(grid_ew(rows * W)), dim3(256), 0, (hipStream_t)stream, x, rows,
+                           W, y);
+    }
+    UBPL_LAUNCH_CHECK();
+    return 0;
+}
 
 UBPL_API int ubpl_maxpool2x2_forward(const float* x, int64_t planes, int H, int W, float* y, void* stream) {
     const int64_t n = planes * (H / 2) * (W / 2);

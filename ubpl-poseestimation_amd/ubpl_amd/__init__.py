@@ -12,5 +12,7 @@ There is no CPU fallback: every compute entry point raises without the HIP
 library or a GPU.
 """
 from . import _lib  # noqa: F401
+from .predict import Predictor  # noqa: F401
 
-__all__ = ["hourglass", "losses", "parameters", "process", "evaluation", "sampler", "tools", "train", "dist"]
+__all__ = ["hourglass", "losses", "parameters", "process", "evaluation", "sampler", "tools", "train", "dist",
+           "predict", "Predictor"]

@@ -32,6 +32,7 @@ SIGNATURES = {
     "ubpl_fdl_cov_forward": (I, [P, P, P, I, I, I, I, P, P, P, P, P, P]),
     "ubpl_fdl_cov_backward": (I, [P, P, P, P, P, P, P, P, I, I, I, I, P, P, I, P]),
     "ubpl_decode_heatmaps": (I, [P, I, I, I, I, P, P, P, P, P]),
+    "ubpl_decode_heatmaps_flip": (I, [P, P, L, I, I, I, I, P, P, P, P, P, P, P]),
     "ubpl_pck": (I, [P, P, I, I, I, I, F, P, P, P, P, P]),
     "ubpl_ema_update": (I, [P, P, L, D, P]),
     "ubpl_adamw_step": (I, [P, P, P, P, L, D, D, D, D, D, L, P]),
@@ -42,6 +43,7 @@ SIGNATURES = {
     "ubpl_bn_part_doubles": (L, [I, I]),
     "ubpl_bn_forward_stats": (I, [P, I, I, I, P, P, F, F, P, P, P, P, P, P, P, P]),
     "ubpl_bn_eval_coeffs": (I, [P, P, P, P, F, I, P, P, P]),
+    "ubpl_bn_eval_coeffs_table": (I, [P, P, P, I, F, P, P]),
     "ubpl_bn_apply": (I, [P, I, I, I, P, P, I, P, P]),
     "ubpl_bn_partial_floats": (L, [I, L]),
     "ubpl_bn_partials": (I, [P, I, I, I, P, P]),
@@ -77,6 +79,7 @@ SIGNATURES = {
     "ubpl_conv1x1_split_load_preferred": (I, [I, I, I, I]),
     "ubpl_conv1x1_split_load_preferred_min": (I, [I, I, I, I, I]),
     "ubpl_conv1x1_forward_split_load": (I, [P, I, I, I, P, L, P, I, P, P, P, P, P, P, P, I, P, I, P]),
+    "ubpl_fliplr": (I, [P, L, I, I, P, P]),
     "ubpl_maxpool2x2_forward": (I, [P, L, I, I, P, P]),
     "ubpl_maxpool2x2_backward": (I, [P, P, L, I, I, P, I, P]),
     "ubpl_avgpool2x2_forward": (I, [P, L, I, I, P, P]),

@@ -149,6 +149,78 @@ class _Node(nn.Module):
         raise RuntimeError("structural node")
 
 
+class _WeightSet:
+    """What a forward reads of a network's weights: the flat parameters (biases, BN
+    affine, the weights the f32 1x1 kernel takes as they are), the split tables and
+    buffers (`wsp[mode]`, StackedHourglass._build_weight_tables) and the f32 re-layouts
+    (`wlay[key]`), for the conv precision `pieces`.
+
+    The model's own set aliases flat_params and is re-laid out by every forward.  A
+    frozen set (StackedHourglass.freeze) owns copies of the forward's part of it — the
+    mode-0 split buffers, the f32 re-layouts the forward reads, the stem's
+    space-to-depth split weights (`stem`) and one coefficient buffer (`coef`, the
+    executor's scale|shift|mean|invstd blocks with scale and shift filled) — all
+    written by refresh() alone, in place, so a captured graph that reads them stays
+    valid across refreshes."""
+
+    def __init__(self, offs, params, wsp, wlay, pieces):
+        self.offs, self.params, self.wsp, self.wlay, self.pieces = offs, params, wsp, wlay, pieces
+        self.frozen, self.source = False, None
+        self.stem = self.coef = self.bn_table = None
+
+    def P(self, name):
+        s, n, shp = self.offs[name]
+        return self.params[s:s + n].view(shp)
+
+    def relayout(self, mode):
+        if self.pieces:
+            for tbl, plane, _, buf, pieces in self.wsp[mode]:
+                Kn.conv_weights_split(self.params, buf, plane, tbl, mode, pieces)
+            tbl, buf, _, m = self.wlay[("rest", mode)]
+            if tbl.shape[0]:
+                Kn.conv_weights_relayout(self.params, buf, tbl, m)
+            return
+        tbl, buf, _, m = self.wlay[mode]
+        Kn.conv_weights_relayout(self.params, buf, tbl, m)
+
+    def W(self, mode, name):
+        key = ("rest", mode) if self.pieces else mode
+        _, buf, idx, _ = self.wlay[key]
+        o, shp = idx[name]
+        return buf[o:o + shp[0] * shp[1] * shp[2]].view(shp)
+
+    def SW(self, mode, name):
+        """Split weights of a conv (None when it is not on the split path)."""
+        if not self.pieces:
+            return None
+        for _, plane, idx, buf, pieces in self.wsp[mode]:
+            if name in idx:
+                o, shp = idx[name]
+                return Kn.SplitWeights(buf, plane, o, shp, pieces)
+        return None
+
+    def stem_split(self, npieces):
+        """The stem's space-to-depth split weights: a frozen set's own, else split now."""
+        if self.stem is not None:
+            return self.stem
+        return Kn.stem_weight_s2d_split(self.P("pre.0.conv.weight"), npieces)
+
+    def refresh(self):
+        """Frozen sets: take the source model's current parameters and running statistics —
+        one copy, the batched split / re-layout launches, the stem split and ONE
+        coefficient launch for every BatchNorm."""
+        if not self.frozen:
+            raise RuntimeError("ubpl_amd: the model's own weight set follows its parameters; only a frozen set "
+                               "is refreshed")
+        m = self.source
+        self.params.copy_(m.flat_params)
+        self.relayout(0)
+        self.relayout(1)               # (the k-major 1x1 weights; a frozen set has no mode-1 split tables)
+        if self.stem is not None:
+            Kn.stem_weight_s2d_split(self.P("pre.0.conv.weight"), self.stem.npieces, out=self.stem)
+        Kn.bn_eval_coeffs_table(self.params, m.flat_stats, self.bn_table, BN_EPS, self.coef)
+
+
 # ---------------------------------------------------------------------------
 # The model
 # ---------------------------------------------------------------------------
@@ -333,33 +405,63 @@ class StackedHourglass(nn.Module):
                     o += (n + 3) // 4 * 4
                 tbl = torch.tensor(rows, dtype=torch.int64).reshape(-1, 5).to(device)
                 self._wlay[key] = (tbl, torch.empty(max(o, 4), device=device), idx, mode)
+        self._wset = _WeightSet(offs, self.flat_params, self._wsp, self._wlay, self.conv_pieces)
 
     def relayout_weights(self, mode):
-        if self.conv_pieces:
-            for tbl, plane, _, buf, pieces in self._wsp[mode]:
-                Kn.conv_weights_split(self.flat_params, buf, plane, tbl, mode, pieces)
-            tbl, buf, _, m = self._wlay[("rest", mode)]
-            if tbl.shape[0]:
-                Kn.conv_weights_relayout(self.flat_params, buf, tbl, m)
-            return
-        tbl, buf, _, m = self._wlay[mode]
-        Kn.conv_weights_relayout(self.flat_params, buf, tbl, m)
+        self._wset.relayout(mode)
 
     def W(self, mode, name):
-        key = ("rest", mode) if self.conv_pieces else mode
-        _, buf, idx, _ = self._wlay[key]
-        o, shp = idx[name]
-        return buf[o:o + shp[0] * shp[1] * shp[2]].view(shp)
+        return self._wset.W(mode, name)
 
     def SW(self, mode, name):
         """Split weights of a conv (None when it is not on the split path)."""
-        if not self.conv_pieces:
-            return None
-        for _, plane, idx, buf, pieces in self._wsp[mode]:
-            if name in idx:
-                o, shp = idx[name]
-                return Kn.SplitWeights(buf, plane, o, shp, pieces)
-        return None
+        return self._wset.SW(mode, name)
+
+    def _coef_index(self):
+        """({BN name: (offset, C)}, total channels) of a forward's coefficient buffer: per BN
+        4*C floats, scale|shift|mean|invstd."""
+        cidx, o = {}, 0
+        for b in self._bn_names:
+            c = self._offs[b + ".weight"][1]
+            cidx[b] = (o, c)
+            o += 4 * c
+        return cidx, o // 4
+
+    def freeze(self):
+        """A private, frozen copy of what an eval forward reads of the weights (see
+        _WeightSet): filled by its refresh(), read by forward_frozen.  Nothing of the
+        model is touched, then or later."""
+        own = self._wset
+        keys = [("rest", 0), ("rest", 1)] if own.pieces else [0, 1]
+        wsp = {0: [[tbl, plane, idx, torch.empty_like(buf), pieces] for tbl, plane, idx, buf, pieces in own.wsp[0]],
+               1: []}          # (the data-gradient tables are no part of a frozen set)
+        wlay = {k: (own.wlay[k][0], torch.empty_like(own.wlay[k][1])) + own.wlay[k][2:] for k in keys}
+        ws = _WeightSet(self._offs, torch.empty_like(self.flat_params), wsp, wlay, own.pieces)
+        cidx, C = self._coef_index()
+        ws.coef = torch.zeros(4 * C, device=self._device)
+        rows = []
+        for b in self._bn_names:
+            s, c = self._sidx[b]
+            rows.append((self._offs[b + ".weight"][0], self._offs[b + ".bias"][0], s, s + c, cidx[b][0], c))
+        ws.bn_table = Kn.bn_coeff_table(rows, self.n_total, self.flat_stats.numel(), 4 * C).to(self._device)
+        if own.pieces in (1, 2, 3) and _STEM_S2D:
+            cout, np_ = self._offs["pre.0.conv.weight"][2][0], Kn.backward_pieces(own.pieces)
+            ws.stem = Kn.SplitWeights(torch.empty(np_ * cout * 256, dtype=torch.int16, device=self._device),
+                                      cout * 256, 0, (cout, 16, 16), np_)
+        ws.frozen, ws.source = True, self
+        ws.refresh()
+        return ws
+
+    def forward_frozen(self, imgs, wset):
+        """The eval forward from a frozen weight set (freeze()): preds [B,S,K,R,R] alone (no
+        feature projection); no weight re-layout, stem-weight split or coefficient launch."""
+        _lib.require_gpu(imgs)
+        if imgs.dtype != torch.float32 or not imgs.is_contiguous():
+            raise TypeError("imgs must be contiguous float32")
+        if not getattr(wset, "frozen", False) or wset.source is not self:
+            raise ValueError("ubpl_amd: forward_frozen takes a weight set of this model's freeze()")
+        with torch.no_grad():
+            return self._forward_impl(imgs, save=False, wset=wset)[0]
 
     def alt_grad_buffer(self):
         """Second gradient buffer for a backward pass that runs concurrently with
@@ -445,23 +547,27 @@ class StackedHourglass(nn.Module):
             self._ws[("coef", B)] = torch.empty(3 * 512 + 4, device=self.flat_params.device)
         return self._ws[key]
 
-    def _forward_impl(self, imgs, save):
+    def _forward_impl(self, imgs, save, wset=None):
+        """wset: a frozen weight set (freeze()) — an eval forward whatever the training
+        flag, with no re-layout, no coefficient launches and no feature projection."""
         B = imgs.shape[0]
         dev = imgs.device
         part = self._scratch(B, 64)
         if save:
             self._grad_keep = []     # the last step's upstream gradients (its streams joined since)
-        ex = _Exec(self, B, dev, part, train=self.training, save=save)
+        frozen = wset is not None
+        train = self.training and not frozen
+        ex = _Exec(self, B, dev, part, train=train, save=save, wset=wset)
         if _RELAYOUT_ONCE and save:
             raise RuntimeError("UBPL_RELAYOUT_ONCE is a forwards-only diagnostic: a training forward's weights "
                                "change every step, the once-laid-out copies would go stale")
-        if not (_RELAYOUT_ONCE and getattr(self, "_relaid", False)):
+        if not frozen and not (_RELAYOUT_ONCE and getattr(self, "_relaid", False)):
             self.relayout_weights(0)
             self.relayout_weights(1)       # k-major 1x1 weights for conv1x1_forward_kmajor
             self._relaid = True
-        if self.training:
+        if train:
             self._nbt.add_(1)
-        else:
+        elif not frozen:
             ex.eval_coeffs()
         x = ex.stem(imgs)
         x = ex.residual("pre.1", x)
@@ -477,7 +583,7 @@ class StackedHourglass(nn.Module):
             hg = ex.hourglass("hgs.%d.0" % i, 4, x)
             f0 = ex.residual("features.%d.0" % i, hg)
             f = ex.conv_bn_relu("features.%d.1" % i, f0)
-            if self.mode != "default":
+            if self.mode != "default" and not frozen:
                 feats.append(Kn.avgpool2x2(f) if self.mode == "AvgPool" else Kn.maxpool2x2(f))
             pr = ex.conv("preds.%d.conv" % i, f)
             preds.append(pr)
@@ -546,8 +652,11 @@ class _HourglassFn(torch.autograd.Function):
 # Executor: one forward pass (+ its saved tensors) and its backward
 # ---------------------------------------------------------------------------
 class _Exec:
-    def __init__(self, model, B, dev, part, train, save):
+    def __init__(self, model, B, dev, part, train, save, wset=None):
         self.m, self.B, self.dev, self.part, self.train, self.do_save = model, B, dev, part, train, save
+        # the weights the forward reads: the model's own set, or a frozen one (its re-layouts,
+        # stem split and eval coefficients made by its refresh(), none of them here)
+        self.ws = model._wset if wset is None else wset
         # backward on another stream into the alternate gradient buffer (train.py sets
         # model._bwd_stream around a student's second-view forward)
         self.bwd_stream = getattr(model, "_bwd_stream", None) if save else None
@@ -562,13 +671,9 @@ class _Exec:
         self.saved = {}
         self.saved_split = {}
         self._rp = None     # (tensor, BN partials of it) from its producer, for the next residual's bn1
-        C = sum(self.m._offs[b + ".weight"][1] for b in self.m._bn_names)
-        self.coef = torch.empty(4 * C, device=dev)     # per BN: scale|shift|mean|invstd
-        self.cidx, o = {}, 0
-        for b in self.m._bn_names:
-            c = self.m._offs[b + ".weight"][1]
-            self.cidx[b] = (o, c)
-            o += 4 * c
+        self.cidx, C = model._coef_index()
+        # per BN: scale|shift|mean|invstd
+        self.coef = self.ws.coef if self.ws.frozen else torch.empty(4 * C, device=dev)
 
     # ---- bookkeeping
     def save(self, key, val):
@@ -600,7 +705,7 @@ class _Exec:
         for b in self.m._bn_names:
             sc, sh, _, _ = self.bnc(b)
             rm, rv = self.m.stats(b)
-            Kn.bn_eval_coeffs(self.m.P(b + ".weight"), self.m.P(b + ".bias"), rm, rv, BN_EPS, sc, sh)
+            Kn.bn_eval_coeffs(self.ws.P(b + ".weight"), self.ws.P(b + ".bias"), rm, rv, BN_EPS, sc, sh)
 
     def bn(self, name, x, part=None):
         """Train: batch statistics (+ running-stat update) — from the partials
@@ -609,7 +714,7 @@ class _Exec:
         sc, sh, mu, istd = self.bnc(name)
         if self.train:
             rm, rv = self.m.stats(name)
-            g, b = self.m.P(name + ".weight"), self.m.P(name + ".bias")
+            g, b = self.ws.P(name + ".weight"), self.ws.P(name + ".bias")
             if part is not None:
                 Kn.bn_stats_from_partials(part, x.shape[1], x.shape[0] * x[0, 0].numel(), g, b, BN_EPS,
                                           BN_MOMENTUM, rm, rv, mu, istd, sc, sh)
@@ -625,15 +730,15 @@ class _Exec:
         return (y, part) if stats else y
 
     def _conv(self, name, x, stride, pro, res, out, stats):
-        w = self.m.P(name + ".weight")
-        b = self.m.P(name + ".bias")
+        w = self.ws.P(name + ".weight")
+        b = self.ws.P(name + ".bias")
         ps, ph = (None, None) if pro is None else pro
         B, Cout = x.shape[0], w.shape[0]
         mkpart = lambda: (Kn.bn_partial_buffer(Cout, B * x.shape[2] * x.shape[3], x.device)
                           if stats and _FWD_EPI else None)
-        ws = self.m.SW(0, name + ".weight") if stride == 1 else None
+        ws = self.ws.SW(0, name + ".weight") if stride == 1 else None
         if ws is not None and ws.npieces in (1, 2, 3) and ws.shape[1] == 1:
-            if Kn.conv1x1_split_load_ok(x, ws, small=self.m.conv_pieces == 2):
+            if Kn.conv1x1_split_load_ok(x, ws, small=self.ws.pieces == 2):
                 part = mkpart() if ws.npieces == 3 else None
                 return Kn.conv1x1_forward_split_load(x, ws, b, ps, ph, res=res, out=out, stat_part=part), part
             if ws.npieces in (2, 3):
@@ -653,21 +758,21 @@ class _Exec:
             return Kn.conv2d_forward_psa(xs, ws, b, res=res, out=out, stat_part=part), part
         if w.shape[2] == 1 and stride == 1 and Kn.conv1x1_kmajor_ok(x, w.shape[0]):
             part = mkpart()
-            return Kn.conv1x1_forward_kmajor(x, self.m.W(1, name + ".weight"), b, ps, ph, res=res, out=out,
+            return Kn.conv1x1_forward_kmajor(x, self.ws.W(1, name + ".weight"), b, ps, ph, res=res, out=out,
                                              stat_part=part), part
-        wt = self.m.W(0, name + ".weight") if w.shape[2] > 1 else None
+        wt = self.ws.W(0, name + ".weight") if w.shape[2] > 1 else None
         return Kn.conv2d_forward(x, w, b, stride, ps, ph, res=res, out=out, w_tap=wt), None
 
     # ---- layers
     def stem(self, imgs):
-        if self.m.conv_pieces in (1, 2, 3) and _STEM_S2D and Kn.stem_s2d_ok(imgs):
+        if self.ws.pieces in (1, 2, 3) and _STEM_S2D and Kn.stem_s2d_ok(imgs):
             # 7x7/s2 as a 4x4 stride-1 conv over the space-to-depth image, on the split path
             # (6xbf16, also under 2xfp16: the image is its weight gradient's operand), or on
             # bf16 operands (the "bf16" precision)
-            np_ = self.m.bwd_pieces
-            ws = Kn.stem_weight_s2d_split(self.m.P("pre.0.conv.weight"), np_)
+            np_ = Kn.backward_pieces(self.ws.pieces)
+            ws = self.ws.stem_split(np_)
             xs = Kn.stem_s2d_split(imgs, 2, np_)
-            y0 = Kn.conv2d_forward_psa(xs, ws, self.m.P("pre.0.conv.bias"))
+            y0 = Kn.conv2d_forward_psa(xs, ws, self.ws.P("pre.0.conv.bias"))
             if self.do_save and _STEM_WGRAD:
                 self.saved_split["pre.0.conv"] = xs      # the weight gradient's B operand
         else:

@@ -160,6 +160,71 @@ def decode_heatmaps(hm, tinv=None):
     return raw, preds, scores
 
 
+def flip_perm(K, pairs):
+    """Host int32 [K] joint permutation of the flip test's left/right swap
+    (utils/udaap/transforms.py:20-57 flip_back): perm[a] = b, perm[b] = a for
+    every pair, identity elsewhere.  Indices in [0, K), each joint in at most
+    one pair (ValueError otherwise)."""
+    perm = list(range(K))
+    seen = set()
+    for pr in pairs:
+        if len(pr) != 2:
+            raise ValueError("ubpl_amd: a flip pair is two joint indices, got %r" % (pr,))
+        a, b = int(pr[0]), int(pr[1])
+        for j in (a, b):
+            if not 0 <= j < K:
+                raise ValueError("ubpl_amd: flip pair %r names joint %d of %d" % (tuple(pr), j, K))
+        if a == b or a in seen or b in seen:
+            raise ValueError("ubpl_amd: flip pair %r repeats a joint" % (tuple(pr),))
+        seen.update((a, b))
+        perm[a], perm[b] = b, a
+    return torch.tensor(perm, dtype=torch.int32)
+
+
+def decode_heatmaps_flip(hm, hm_flip, sb, N, K, H, W, perm=None, tinv=None, want_merged=False, out=None):
+    """Flip-test decode (ubpl_decode_heatmaps_flip): hm / hm_flip are tensors whose
+    first element is map (0, 0) — views at an element offset, e.g. the last stack of
+    a [B,S,K,H,W] output — with batch stride sb floats; hm_flip None: a plain
+    strided decode.  perm: device int32 [K] (flip_perm(...).to(device)) or None.
+    -> (raw [N,K,2], preds [N,K,2] or None, scores [N,K], merged [N,K,H,W] or None);
+    out = (raw, preds, scores, merged): write into these instead of allocating."""
+    for t, nm in ((hm, "hm"), (hm_flip, "hm_flip")):
+        if t is None:
+            continue
+        _chk(t, nm)
+        if t.numel() < (N - 1) * sb + K * H * W:
+            raise ValueError("ubpl_amd: %s holds %d floats, %d maps of stride %d need %d"
+                             % (nm, t.numel(), N, sb, (N - 1) * sb + K * H * W))
+    _chk(perm, "perm", torch.int32)
+    _chk(tinv, "tinv", torch.float64)
+    if perm is not None and perm.numel() != K:
+        raise ValueError("ubpl_amd: perm has %d entries for %d joints" % (perm.numel(), K))
+    dev = hm.device
+    if out is not None:
+        raw, preds, scores, merged = out
+    else:
+        raw = torch.empty((N, K, 2), device=dev, dtype=F32)
+        preds = torch.empty((N, K, 2), device=dev, dtype=F32) if tinv is not None else None
+        scores = torch.empty((N, K), device=dev, dtype=F32)
+        merged = torch.empty((N, K, H, W), device=dev, dtype=F32) if want_merged else None
+    call("ubpl_decode_heatmaps_flip", _p(hm), _p(hm_flip), int(sb), N, K, H, W, _p(perm), _p(tinv), _p(merged),
+         _p(raw), _p(preds), _p(scores))
+    return raw, preds, scores, merged
+
+
+def fliplr(x, out=None):
+    """ProcessUtils.image_fliplr on device planes: x [..., H, W] -> x mirrored along W
+    (out: a different tensor of x's size)."""
+    _chk(x, "x")
+    y = torch.empty_like(x) if out is None else out
+    _chk(y, "out")
+    if y.numel() != x.numel() or y.data_ptr() == x.data_ptr():
+        raise ValueError("ubpl_amd: fliplr writes a different tensor of the input's size")
+    H, W = x.shape[-2], x.shape[-1]
+    call("ubpl_fliplr", _p(x), x.numel() // max(H * W, 1), H, W, _p(y))
+    return y
+
+
 def pck(preds, gts, ref, thr):
     _chk(preds, "preds")
     _chk(gts, "gts")
@@ -229,6 +294,24 @@ def bn_forward_stats(x, gamma, beta, eps, momentum, rmean, rvar, part, mean, inv
 def bn_eval_coeffs(gamma, beta, rmean, rvar, eps, scale, shift):
     call("ubpl_bn_eval_coeffs", _p(gamma), _p(beta), _p(rmean), _p(rvar), float(eps), gamma.numel(), _p(scale),
          _p(shift))
+
+
+def bn_coeff_table(rows, n_params, n_stats, n_coef):
+    """Host int64 [nbn,6] table of ubpl_bn_eval_coeffs_table from rows (gamma_off,
+    beta_off, rmean_off, rvar_off, coef_off, C), every offset checked against the
+    buffers' sizes (the kernel trusts the table)."""
+    t = torch.tensor(rows, dtype=torch.int64).reshape(-1, 6)
+    for g, b, rm, rv, co, c in t.tolist():
+        if c < 1 or min(g, b, rm, rv, co) < 0 or max(g, b) + c > n_params or max(rm, rv) + c > n_stats \
+                or co + 2 * c > n_coef:
+            raise ValueError("ubpl_amd: BatchNorm table row %r reaches outside params[%d] / stats[%d] / coef[%d]"
+                             % ((g, b, rm, rv, co, c), n_params, n_stats, n_coef))
+    return t
+
+
+def bn_eval_coeffs_table(params, stats, table, eps, coef):
+    """scale | shift of every BatchNorm of `table` (bn_coeff_table(...).to(device)) in one launch."""
+    call("ubpl_bn_eval_coeffs_table", _p(params), _p(stats), _p(table), int(table.shape[0]), float(eps), _p(coef))
 
 
 def bn_apply(x, scale, shift, relu, out=None):
@@ -539,13 +622,19 @@ def stem_s2d_split(x, pad=2, npieces=3):
     return SplitAct(buf, plane, B, 16, Ho, Wo, pad, npieces)
 
 
-def stem_weight_s2d_split(w, npieces=3):
-    """The stem's 7x7 weights as the split 4x4 weights of its space-to-depth conv."""
+def stem_weight_s2d_split(w, npieces=3, out=None):
+    """The stem's 7x7 weights as the split 4x4 weights of its space-to-depth conv
+    (out: an earlier result of the same shape, rewritten in place)."""
     Cout, C, KS, _ = w.shape
     plane = Cout * 16 * 16
-    buf = torch.empty(npieces * plane, device=w.device, dtype=torch.int16)
+    if out is not None:
+        if (out.plane, out.shape, out.npieces, out.off) != (plane, (Cout, 16, 16), npieces, 0):
+            raise ValueError("ubpl_amd: stem split buffer of another shape")
+        buf = out.buf
+    else:
+        buf = torch.empty(npieces * plane, device=w.device, dtype=torch.int16)
     call("ubpl_stem_weight_s2d_split", _p(w.contiguous()), Cout, C, KS, int(npieces), _p(buf), int(plane))
-    return SplitWeights(buf, plane, 0, (Cout, 16, 16), npieces)
+    return SplitWeights(buf, plane, 0, (Cout, 16, 16), npieces) if out is None else out
 
 
 _NO_SOL = os.environ.get("UBPL_NO_SOL") == "1"      # diagnostic: every 1x1 on the exact-f32 kernels

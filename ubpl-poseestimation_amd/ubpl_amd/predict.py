@@ -1,0 +1,226 @@
+"""Inference with trained networks: images -> keypoints.
+
+`Predictor` is what a user of a trained teacher runs.  It follows the
+reference's validation (projects/MT_UBPL.py:355-408: per-network argmax decode
++ inverse transform, and the coordinate mean of the networks, :387) and adds
+the stacked-hourglass flip test the reference carries the pieces of without
+wiring them in (utils/augment.py:239-252 fliplr_back / fliplr_back_tensor,
+utils/udaap/transforms.py:20-57 flip_back).
+
+Three things make it cheap at small batches:
+
+* frozen weights — a private snapshot per network (StackedHourglass.freeze):
+  the split / re-laid-out conv weights, the stem's space-to-depth weights and
+  the eval coefficients of every BatchNorm (one ubpl_bn_eval_coeffs_table
+  launch) are made by refresh() and only read by predict();
+* the flip test in two kernels — ubpl_fliplr writes the mirrored half of one
+  [2N] batch, ubpl_decode_heatmaps_flip flips back, swaps the pairs, averages
+  and decodes the last stack of the network's output in place;
+* graph replay — per batch size, the frozen forwards, the flip, the decode and
+  the mean are captured in one HIP graph on ONE stream (several networks run
+  one after another: no fork inside the capture) and replayed.
+
+There is no CPU fallback.
+"""
+import os
+from collections import OrderedDict
+
+import torch
+
+from . import _lib
+from . import kernels as Kn
+
+
+class _Slot:
+    """Static buffers of one (batch size, resolution, heatmaps wanted) and, once
+    captured, the graph that maps its inputs to its outputs."""
+
+    def __init__(self, M, N, K, R, flip, want_hm, dev):
+        H = W = R // 4
+        f32 = dict(device=dev, dtype=torch.float32)
+        self.N, self.H, self.W = N, H, W
+        self.batch = torch.zeros((2 * N if flip else N, 3, R, R), **f32)
+        self.imgs = self.batch[:N]
+        self.tinv = torch.zeros((N, 6), device=dev, dtype=torch.float64)
+        self.raw = torch.zeros((M, N, K, 2), **f32)
+        self.preds = torch.zeros((M, N, K, 2), **f32)
+        self.scores = torch.zeros((M, N, K), **f32)
+        self.mean = torch.zeros((N, K, 2), **f32)
+        self.heatmaps = torch.zeros((M, N, K, H, W), **f32) if want_hm else None
+        self.graph = None
+
+    def release(self):
+        if self.graph is not None:
+            self.graph.reset()
+            self.graph = None
+
+
+class Predictor:
+    """Predictor(models, flip_test=False, flip_pairs=None, max_batch=32, max_graphs=4, graph=None)
+
+    models      one StackedHourglass or a list (the teachers), same k, one device;
+    flip_test   average each heatmap with the flipped-back heatmap of the mirrored image;
+    flip_pairs  [(left, right), ...] joints swapped when flipping back (the caller's
+                dataset convention; None = none, the reference's kps_fliplr convention,
+                utils/process.py:239-242);
+    max_batch   larger inputs run in chunks of this size;
+    max_graphs  captured graphs kept (one per exact batch size, least recently used out);
+    graph       None: on unless UBPL_PREDICT_GRAPH=0; False: the same path eagerly.
+
+    Snapshot semantics: construction and refresh() copy the networks' parameters and
+    running statistics into private frozen weight sets; training steps, EMA updates or
+    load_state_dict on the networks change nothing here until the next refresh().  The
+    networks' training flag, statistics, counters, parameters and own weight buffers are
+    never touched."""
+
+    def __init__(self, models, flip_test=False, flip_pairs=None, max_batch=32, max_graphs=4, graph=None):
+        _lib.require_gpu()
+        from .hourglass import StackedHourglass
+        self.models = [models] if isinstance(models, StackedHourglass) else list(models)
+        if not self.models or not all(isinstance(m, StackedHourglass) for m in self.models):
+            raise TypeError("ubpl_amd: Predictor takes a StackedHourglass or a list of them")
+        self.k = self.models[0].k
+        self.device = self.models[0].flat_params.device
+        if any(m.k != self.k or m.flat_params.device != self.device for m in self.models):
+            raise ValueError("ubpl_amd: the networks of a Predictor share k and the device")
+        if max_batch < 1 or max_graphs < 1:
+            raise ValueError("ubpl_amd: max_batch and max_graphs are at least 1")
+        self.flip_test = bool(flip_test)
+        self.perm = None
+        if flip_pairs:
+            self.perm = Kn.flip_perm(self.k, flip_pairs).to(self.device)
+        self.max_batch, self.max_graphs = int(max_batch), int(max_graphs)
+        self.use_graph = os.environ.get("UBPL_PREDICT_GRAPH", "1") != "0" if graph is None else bool(graph)
+        self._slots = OrderedDict()
+        self._sets = None
+        self.refresh()
+
+    # -- weights ----------------------------------------------------------
+    def refresh(self):
+        """Take the networks' current parameters and running statistics.  The frozen
+        buffers are rewritten in place, so captured graphs stay; a network whose conv
+        precision changed gets a new frozen set and the graphs are dropped."""
+        with torch.cuda.device(self.device), torch.no_grad():
+            if self._sets is not None and all(ws.pieces == m.conv_pieces for ws, m in zip(self._sets, self.models)):
+                for ws in self._sets:
+                    ws.refresh()
+                return
+            self.release()
+            self._sets = [m.freeze() for m in self.models]
+
+    def release(self):
+        """Drop every captured graph and its static buffers (their pools go with them)."""
+        for s in self._slots.values():
+            s.release()
+        if self._slots:
+            self._slots.clear()
+            torch.cuda.empty_cache()
+
+    # -- one batch --------------------------------------------------------
+    def _run(self, s):
+        """The device work of one batch, on the current stream: static inputs of slot s
+        -> its static outputs."""
+        N, K = s.N, self.k
+        if self.flip_test:
+            Kn.fliplr(s.imgs, out=s.batch[N:])
+        for mi, (m, ws) in enumerate(zip(self.models, self._sets)):
+            o = m.forward_frozen(s.batch, ws)                       # [N or 2N, S, K, H, W]
+            S, H, W = o.shape[1], o.shape[3], o.shape[4]
+            if (H, W) != (s.H, s.W):
+                raise RuntimeError("ubpl_amd: heatmaps %dx%d, expected %dx%d" % (H, W, s.H, s.W))
+            sb, last = S * K * H * W, (S - 1) * K * H * W
+            flat = o.reshape(-1)
+            # the last stack of rows 0..N and N..2N, in place: row stride + base offset
+            hm = flat[last:]
+            hm_flip = flat[N * sb + last:] if self.flip_test else None
+            Kn.decode_heatmaps_flip(hm, hm_flip, sb, N, K, H, W, self.perm, s.tinv,
+                                    out=(s.raw[mi], s.preds[mi], s.scores[mi],
+                                         s.heatmaps[mi] if s.heatmaps is not None else None))
+        s.mean.copy_(torch.stack(list(s.preds), -1).mean(-1))       # projects/MT_UBPL.py:387
+
+    def _slot(self, N, R, want_hm):
+        key = (N, R, want_hm)
+        s = self._slots.get(key)
+        if s is not None:
+            self._slots.move_to_end(key)
+            return s, False
+        while len(self._slots) >= self.max_graphs:
+            _, old = self._slots.popitem(last=False)
+            old.release()
+            del old
+            torch.cuda.empty_cache()
+        s = self._slots[key] = _Slot(len(self.models), N, self.k, R, self.flip_test, want_hm, self.device)
+        return s, True
+
+    def _predict_chunk(self, imgs, tinv, want_hm):
+        N, R = imgs.shape[0], imgs.shape[2]
+        s, new = self._slot(N, R, want_hm)
+        s.imgs.copy_(imgs, non_blocking=True)
+        if tinv is not None:
+            s.tinv.copy_(tinv, non_blocking=True)
+        if not self.use_graph:
+            self._run(s)
+        else:
+            if new:
+                # warm-up: the networks' per-batch-size scratch is allocated here, outside the
+                # graph's pool; then the capture (which records, it does not execute)
+                self._run(s)
+                torch.cuda.synchronize(self.device)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    self._run(s)
+                s.graph = g
+            s.graph.replay()
+        out = {"raw": s.raw.clone(), "scores": s.scores.clone(),
+               "preds": s.preds.clone() if tinv is not None else None,
+               "preds_mean": s.mean.clone() if tinv is not None else None}
+        if want_hm:
+            out["heatmaps"] = s.heatmaps.clone()
+        return out
+
+    def predict(self, imgs, center=None, scale=None, return_heatmaps=False, out_res=None):
+        """imgs float32 [N,3,R,R] (host or device) -> dict of device tensors, the caller's own:
+        raw [M,N,K,2] 1-based heatmap coordinates, scores [M,N,K], preds [M,N,K,2] and
+        preds_mean [N,K,2] in image coordinates (None without center / scale), and with
+        return_heatmaps heatmaps [M,N,K,H,W], the (flip-merged) last-stack maps; M networks.
+        out_res: the resolution of the inverse transform (default: the heatmaps')."""
+        if not torch.is_tensor(imgs) or imgs.dtype != torch.float32 or imgs.dim() != 4 or imgs.shape[1] != 3 \
+                or imgs.shape[2] != imgs.shape[3] or imgs.shape[0] < 1:
+            raise TypeError("ubpl_amd: predict takes float32 images [N,3,R,R], N >= 1")
+        if (center is None) != (scale is None):
+            raise ValueError("ubpl_amd: center and scale come together")
+        N, R = imgs.shape[0], imgs.shape[2]
+        tinv = None
+        if center is not None:
+            from .process import inverse_transforms
+            res = [R // 4, R // 4] if out_res is None else [out_res, out_res]
+            tinv = inverse_transforms(center, scale, res)
+            if tinv.shape[0] != N:
+                raise ValueError("ubpl_amd: %d centers for %d images" % (tinv.shape[0], N))
+        imgs = imgs.contiguous()
+        outs = []
+        with torch.cuda.device(self.device), torch.no_grad():
+            for a in range(0, N, self.max_batch):
+                b = min(N, a + self.max_batch)
+                outs.append(self._predict_chunk(imgs[a:b], None if tinv is None else tinv[a:b], bool(return_heatmaps)))
+        if len(outs) == 1:
+            return outs[0]
+        return {k: None if outs[0][k] is None else torch.cat([o[k] for o in outs], 0 if k == "preds_mean" else 1)
+                for k in outs[0]}
+
+    def validate(self, loader, args):
+        """train.validate(loader, models, args) from the frozen snapshot: the same triple
+        (predsArray, accs_records, errs_records), folded by the same code.  Single process
+        only: under torch.distributed this raises NotImplementedError (train.validate shards
+        and gathers the batches)."""
+        from . import dist as D
+        from . import train as T
+        if D.is_dist():
+            raise NotImplementedError("ubpl_amd: Predictor.validate runs in one process; use train.validate "
+                                      "under torch.distributed")
+        rows = []
+        for imgMap, _, meta in loader:
+            out = self.predict(imgMap.float(), meta["center"], meta["scale"], out_res=args.outRes)
+            pm = list(out["preds"]) + [out["preds_mean"]]
+            rows.append(T.valid_batch_row(pm, meta, self.device, args))
+        return T.fold_valid_rows(rows, len(self.models) + 1)

@@ -1162,6 +1162,40 @@ def gather_valid_rows(rows):
                   key=lambda r: r[0])
 
 
+def valid_batch_row(pm, meta, dev, args):
+    """One validation batch's row (batch_index or None, bs, k, host tensor): the PCK
+    errs | accs of every entry of pm (the teachers' transformed predictions and their
+    mean, each [bs,k,2] on the device) followed by the predictions themselves, in one
+    device->host copy."""
+    from .evaluation import EvaluationUtils
+    bs, k = meta["kpsMap"].shape[:2]
+    gts = meta["kpsMap"].to(dev).float().contiguous()
+    outs = [EvaluationUtils.acc_pck(p, gts, args.pck_ref, args.pck_thr) for p in pm]
+    host = torch.cat([torch.cat([er, ac]) for er, ac in outs] + [p.reshape(-1) for p in pm]).cpu()
+    return meta.get("batch_index"), bs, k, host
+
+
+def fold_valid_rows(rows, n):
+    """Rows of valid_batch_row (n entries each) -> (predsArray, accs_records,
+    errs_records) with the reference's weights (projects/MT_UBPL.py:393-397: bs per
+    keypoint entry, bs*k for the mean entry)."""
+    from .losses import AvgCounters
+    accs_c = [AvgCounters() for _ in range(n)]
+    errs_c = [AvgCounters() for _ in range(n)]
+    preds_arr = [[] for _ in range(n)]
+    for _, bs, k, host in rows:
+        for mi in range(n):
+            errs = host[mi * 2 * (k + 1):mi * 2 * (k + 1) + k + 1]
+            accs = host[mi * 2 * (k + 1) + k + 1:(mi + 1) * 2 * (k + 1)]
+            for idx in range(k + 1):
+                accs_c[mi].update(idx, accs[idx].item(), bs if idx < k else bs * k)
+                errs_c[mi].update(idx, errs[idx].item(), bs if idx < k else bs * k)
+        base = n * 2 * (k + 1)
+        for mi in range(n):
+            preds_arr[mi] += host[base + mi * bs * k * 2:base + (mi + 1) * bs * k * 2].reshape(bs, k, 2).tolist()
+    return preds_arr, [c.avg() for c in accs_c], [c.avg() for c in errs_c]
+
+
 def validate(validLoader, models_ema, args):
     """projects/MT_UBPL.py:355-408 -> (predsArray, accs_records, errs_records);
     entries per teacher plus their mean (brNum + 1).
@@ -1176,19 +1210,16 @@ def validate(validLoader, models_ema, args):
     into the AvgCounters in the single-device batch order, so the records are
     exactly what one device computes (projects/MT_UBPL.py:393-397 weights:
     bs per keypoint entry, bs*k for the mean entry)."""
-    from .evaluation import EvaluationUtils
-    from .losses import AvgCounters
     from .process import inverse_transforms
     n = len(models_ema) + 1
     D.broadcast_buffers(models_ema)
     for e in models_ema:
         e.eval()
     dev = models_ema[0].flat_params.device
-    rows = []                                    # (batch index, bs, k, host row, preds)
+    rows = []                                    # (batch index, bs, k, host row)
     with torch.no_grad():
         for bat, (imgMap, heatmap, meta) in enumerate(validLoader):
             img = imgMap.to(dev, non_blocking=True).float().contiguous()
-            bs, k = meta["kpsMap"].shape[:2]
             tinv = inverse_transforms(meta["center"], meta["scale"], [args.outRes, args.outRes]).to(dev)
             pm = []
             for e in models_ema:
@@ -1197,24 +1228,8 @@ def validate(validLoader, models_ema, args):
                 _, p, _ = Kn.decode_heatmaps(o[:, -1].contiguous(), tinv)
                 pm.append(p)
             pm.append(torch.stack(pm, -1).mean(-1))                   # :387 preds_mean
-            gts = meta["kpsMap"].to(dev).float().contiguous()
-            outs = [EvaluationUtils.acc_pck(p, gts, args.pck_ref, args.pck_thr) for p in pm]
-            host = torch.cat([torch.cat([er, ac]) for er, ac in outs] + [p.reshape(-1) for p in pm]).cpu()
-            rows.append((meta.get("batch_index"), bs, k, host))
-    rows = gather_valid_rows(rows)
-    accs_c = [AvgCounters() for _ in range(n)]
-    errs_c = [AvgCounters() for _ in range(n)]
-    preds_arr = [[] for _ in range(n)]
-    for _, bs, k, host in rows:
-        for mi in range(n):
-            errs = host[mi * 2 * (k + 1):mi * 2 * (k + 1) + k + 1]
-            accs = host[mi * 2 * (k + 1) + k + 1:(mi + 1) * 2 * (k + 1)]
-            for idx in range(k + 1):
-                accs_c[mi].update(idx, accs[idx].item(), bs if idx < k else bs * k)
-                errs_c[mi].update(idx, errs[idx].item(), bs if idx < k else bs * k)
-        base = n * 2 * (k + 1)
-        for mi in range(n):
-            preds_arr[mi] += host[base + mi * bs * k * 2:base + (mi + 1) * bs * k * 2].reshape(bs, k, 2).tolist()
+            rows.append(valid_batch_row(pm, meta, dev, args))
+    out = fold_valid_rows(gather_valid_rows(rows), n)
     for e in models_ema:
         e.train()
-    return preds_arr, [c.avg() for c in accs_c], [c.avg() for c in errs_c]
+    return out
