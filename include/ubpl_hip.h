@@ -98,6 +98,24 @@ int ubpl_decode_heatmaps(const float* hm, int N, int K, int H, int W, const doub
 int ubpl_decode_heatmaps_flip(const float* hm, const float* hm_flip, int64_t sb, int N, int K, int H, int W,
                               const int* perm, const double* tinv, float* merged, float* raw, float* preds,
                               float* scores, void* stream);
+/* UBPL ensemble pseudo-labels at inference: JointPseudoLoss3's target and mask
+ * (utils/losses.py:176-210) from one read of M members' heatmaps.  Member m's
+ * map (n, k) starts at hm + m*sm + n*sb + k*H*W (strides in floats: a
+ * [M,N,K,H,W] buffer, or the last stacks of [M,B,S,K,H,W], in place);
+ * 1 <= M <= 8 (hipErrorInvalidValue otherwise).  Per pixel
+ * T = (((p_0 + p_1) + ...) + p_{M-1}) / (float)M (targets.mean(0), :179), to
+ * mean_hm [N,K,H,W].  Per map: ens_raw / ens_preds [N,K,2], ens_score [N,K] =
+ * the decode of T as ubpl_decode_heatmaps does; member_score [M,N,K] =
+ * max_px p_m (s1 of :187, the member in the student's place); disagree
+ * [M,N,K] = mean_px (p_m - T)^2 (:184), f32, a fixed summation order; select
+ * [M,N,K] = (member_score >= thr) * (ens_score >= thr) as 0/1 (:187-193; a
+ * NaN score never selects).  thr: device f32[1], read by the kernel, so a
+ * captured graph serves every threshold.  tinv, mean_hm and every output but
+ * select are nullable (ens_preds needs tinv). */
+/*@ hm:f32[(M-1)*sm+(N-1)*sb+(int64_t)K*H*W] tinv:f64[N*6] thr:f32[1] mean_hm:f32[(int64_t)N*K*H*W] ens_raw:f32[N*K*2] ens_preds:f32[N*K*2] ens_score:f32[N*K] member_score:f32[(int64_t)M*N*K] disagree:f32[(int64_t)M*N*K] select:f32[(int64_t)M*N*K] */
+int ubpl_ensemble_pseudo(const float* hm, int64_t sm, int64_t sb, int M, int N, int K, int H, int W,
+                         const double* tinv, const float* thr, float* mean_hm, float* ens_raw, float* ens_preds,
+                         float* ens_score, float* member_score, float* disagree, float* select, void* stream);
 /* EvaluationUtils.acc_pck (utils/evaluation.py:91-139).  errs/accs [K+1];
  * hits/valid [K] int32 (nullable) for cross-rank aggregation. */
 /*@ preds:f32[N*K*2] gts:f32[N*K*3] errs:f32[K+1] accs:f32[K+1] hits:i32[K] valid:i32[K] */

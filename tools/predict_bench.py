@@ -18,6 +18,17 @@ median of the rounds is reported, with the spread (max - min) / median across th
 stdout (--out: also written to a file).  No GPU, no number: there is no CPU fallback.
 
     python tools/predict_bench.py [--stacks 2] [--res 256] [--batches 1,8,32] [--out FILE]
+
+--mode pseudo times the ensemble pseudo-labels instead, on ONE Predictor of two teachers
+with the flip test on:
+
+  (p) pseudo    Predictor.pseudo_label(x, center, scale);
+  (q) predict   Predictor.predict(x, center, scale) — what pseudo_label adds is (p) - (q);
+  (r) compose   the same ensemble outputs by torch ops on predict(return_heatmaps=True) and
+                one Kn.decode_heatmaps of the mean — what a user wrote before pseudo_label.
+
+Same warm-up, rounds and report; (p) and (r) must select the same joints before anything
+is timed.
 """
 import argparse
 import json
@@ -39,6 +50,83 @@ def timed(fn, calls):
     return (time.perf_counter() - t0) / calls * 1e3
 
 
+def measure(variants, a):
+    """Warm-up, then a.repeats rounds in which the variants alternate -> {name_ms, name_spread,
+    name_seconds_timed}."""
+    calls = {}
+    for name, fn in variants.items():        # warm-up, and the call count of a round's window
+        timed(fn, 3)
+        calls[name] = max(3, int(a.window * 1e3 / timed(fn, 5)) + 1)
+    ms = {name: [] for name in variants}
+    for _ in range(a.repeats):
+        for name, fn in variants.items():
+            ms[name].append(timed(fn, calls[name]))
+    row = {}
+    for name, v in ms.items():
+        v = sorted(v)
+        med = v[len(v) // 2]
+        row[name + "_ms"] = round(med, 4)
+        row[name + "_spread"] = round((v[-1] - v[0]) / med, 4)
+        row[name + "_seconds_timed"] = round(sum(v) * calls[name] / 1e3, 2)
+    return row
+
+
+def pseudo_main(a):
+    from ubpl_amd import Predictor, _lib, kernels as Kn
+    from ubpl_amd.hourglass import StackedHourglass
+    from ubpl_amd.process import inverse_transforms
+    _lib.require_gpu()
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    gen = torch.Generator().manual_seed(1)
+    models = []
+    for seed in (0, 1):
+        torch.manual_seed(seed)
+        m = StackedHourglass(a.k, a.stacks, "AvgPool")
+        with torch.no_grad():
+            for _ in range(2):                   # running statistics off their initial values
+                m((torch.rand(4, 3, a.res, a.res, generator=gen) - 0.5).to(dev))
+        models.append(m.eval())
+    P = Predictor(models, flip_test=True)
+    rows = []
+    for B in [int(b) for b in a.batches.split(",")]:
+        x = (torch.rand(B, 3, a.res, a.res, generator=gen) - 0.5).to(dev)
+        center = torch.full((B, 2), a.res / 2.0)
+        scale = torch.full((B,), a.res / 200.0)
+        tinv = inverse_transforms(center, scale, [a.res // 4, a.res // 4]).to(dev)
+        # seeded networks score low: the threshold that splits this batch's ensemble scores
+        thr = float(P.pseudo_label(x, center, scale, thr=0.0)["ens_score"].median()) if a.thr <= 0 else a.thr
+
+        def compose():
+            o = P.predict(x, center, scale, return_heatmaps=True)
+            hm = o["heatmaps"]
+            T = hm.mean(0)
+            raw, preds, score = Kn.decode_heatmaps(T, tinv)
+            sel = (hm.flatten(3).amax(-1) >= thr) & (score >= thr)
+            dis = ((hm - T) ** 2).flatten(3).mean(-1)
+            spread = ((o["raw"] - raw) ** 2).sum(-1).sqrt().amax(0)
+            return raw, preds, score, sel, dis, spread, sel.all(0)
+
+        got, want = P.pseudo_label(x, center, scale, thr=thr), compose()
+        if not (torch.equal(got["ens_raw"], want[0]) and torch.equal(got["member_select"], want[3])
+                and torch.equal(got["selected"], want[6])):
+            raise SystemExit("predict_bench: pseudo_label and the torch composition disagree at B=%d" % B)
+        row = {"B": B, "thr": thr, "selected_fraction": round(float(got["selected"].float().mean()), 4)}
+        row.update(measure({"pseudo": lambda: P.pseudo_label(x, center, scale, thr=thr),
+                            "predict": lambda: P.predict(x, center, scale), "compose": compose}, a))
+        row["pseudo_over_predict"] = round(row["pseudo_ms"] / row["predict_ms"], 3)
+        row["compose_over_pseudo"] = round(row["compose_ms"] / row["pseudo_ms"], 3)
+        rows.append(row)
+    out = {"tool": "predict_bench", "mode": "pseudo", "model": "HG%d" % a.stacks, "teachers": len(models),
+           "flip_test": True, "k": a.k, "res": a.res, "precision": Kn.conv_precision_name(), "repeats": a.repeats,
+           "device": torch.cuda.get_device_name(0), "rows": rows}
+    line = json.dumps(out)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--stacks", type=int, default=2)
@@ -48,7 +136,11 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--window", type=float, default=0.25, help="seconds of work per variant per round")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--mode", default="predict", choices=["predict", "pseudo"])
+    ap.add_argument("--thr", type=float, default=0.95, help="--mode pseudo: the score threshold (<= 0: each batch's median ensemble score)")
     a = ap.parse_args()
+    if a.mode == "pseudo":
+        return pseudo_main(a)
 
     from ubpl_amd import Predictor, _lib, kernels as Kn
     from ubpl_amd.hourglass import StackedHourglass
@@ -84,21 +176,8 @@ def main():
         if not (torch.equal(ref[0], got["raw"][0]) and torch.equal(ref[1], got["preds"][0])
                 and torch.equal(ref[2], got["scores"][0])):
             raise SystemExit("predict_bench: the replay and the eager path disagree at B=%d" % B)
-        calls = {}
-        for name, fn in variants.items():        # warm-up, and the call count of a round's window
-            timed(fn, 3)
-            calls[name] = max(3, int(a.window * 1e3 / timed(fn, 5)) + 1)
-        ms = {name: [] for name in variants}
-        for _ in range(a.repeats):
-            for name, fn in variants.items():
-                ms[name].append(timed(fn, calls[name]))
         row = {"B": B}
-        for name, v in ms.items():
-            v = sorted(v)
-            med = v[len(v) // 2]
-            row[name + "_ms"] = round(med, 4)
-            row[name + "_spread"] = round((v[-1] - v[0]) / med, 4)
-            row[name + "_seconds_timed"] = round(sum(v) * calls[name] / 1e3, 2)
+        row.update(measure(variants, a))
         row["replay_speedup"] = round(row["eager_ms"] / row["replay_ms"], 3)
         row["flip_over_2x_replay"] = round(row["flip_ms"] / (2 * row["replay_ms"]), 3)
         rows.append(row)

@@ -19,6 +19,11 @@
 // (utils/augment.py:239-252, utils/udaap/transforms.py:20-57) and the average
 // fused into the one read of both heatmap sets, which are addressed through a
 // batch stride (the last stack of a [B,S,K,H,W] network output, in place).
+//
+// ensemble pseudo-labels (ubpl_ensemble_pseudo): JointPseudoLoss3's target and mask
+// (utils/losses.py:176-210) at inference.  One read of M members' maps gives, per map,
+// the decode of their per-pixel mean T (:179), every member's peak (:187), its mean
+// squared distance from T (:184) and the two-sided threshold mask (:187-193).
 #include "common.h"
 
 namespace {
@@ -31,8 +36,9 @@ __device__ __forceinline__ bool beats(float v, int i, float bv, int bi) {
 }
 
 // The lanes' (value, first index) candidates of one map -> its decoded point,
-// written by lane 0 (the rules in the header comment above).
-__device__ __forceinline__ void finish_map(float bv, int bi, int lane, int map, int W, const double* __restrict__ tinv,
+// written by lane 0 (the rules in the header comment above).  Returns the map's
+// maximum (every lane holds it after the xor butterfly).
+__device__ __forceinline__ float finish_map(float bv, int bi, int lane, int map, int W, const double* __restrict__ tinv,
                                            int K, float* __restrict__ raw, float* __restrict__ preds,
                                            float* __restrict__ scores) {
 #pragma unroll
@@ -44,7 +50,7 @@ __device__ __forceinline__ void finish_map(float bv, int bi, int lane, int map, 
             bi = oi;
         }
     }
-    if (lane != 0) return;
+    if (lane != 0) return bv;
     const float on = bv > 0.f ? 1.f : 0.f;
     const float px = (float)(bi % W + 1) * on;   // utils/udaap/evaluation.py:25,28-29
     const float py = (float)(bi / W + 1) * on;   // :26
@@ -61,6 +67,7 @@ __device__ __forceinline__ void finish_map(float bv, int bi, int lane, int map, 
         preds[map * 2 + 0] = (float)((long long)rx + 1);  // astype(int) + 1 (:158)
         preds[map * 2 + 1] = (float)((long long)ry + 1);
     }
+    return bv;
 }
 
 __global__ void __launch_bounds__(256) argmax_kernel(const float* __restrict__ hm, int maps, int H, int W,
@@ -129,6 +136,84 @@ __global__ void __launch_bounds__(256) argmax_flip_kernel(const float* __restric
         }
     }
     finish_map(bv, bi, lane, map, W, tinv, K, raw, preds, scores);
+}
+
+// max with torch.max's NaN rule: a NaN, once seen, stays.
+__device__ __forceinline__ float nanmax(float a, float b) { return (b > a || isnan(b)) ? b : a; }
+
+// ubpl_ensemble_pseudo: one wave per map (n, k), the M members' values of a pixel in registers.
+// T = (((p_0 + p_1) + ...) + p_{M-1}) / (float)M, a sequential f32 sum in member order and one
+// division (targets.mean(0), utils/losses.py:179); T goes to mean_hm (nullable) and, from the
+// same registers, into the argmax and into (p_m - T)^2.  The squared distances are summed per
+// lane in pixel order and then by a fixed xor butterfly, so repeated launches give equal bits.
+template <int M>
+__global__ void __launch_bounds__(256) ensemble_pseudo_kernel(
+    const float* __restrict__ hm, int64_t sm, int64_t sb, int maps, int H, int W, const double* __restrict__ tinv,
+    int K, const float* __restrict__ thr, float* __restrict__ mean_hm, float* __restrict__ ens_raw,
+    float* __restrict__ ens_preds, float* __restrict__ ens_score, float* __restrict__ member_score,
+    float* __restrict__ disagree, float* __restrict__ select) {
+    const int lane = threadIdx.x & 63;
+    const int map = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (map >= maps) return;
+    const int HW = H * W;
+    const int n = map / K, k = map - n * K;
+    const float* a = hm + n * sb + (int64_t)k * HW;
+    float* mo = mean_hm != nullptr ? mean_hm + (int64_t)map * HW : nullptr;
+    float mx[M], sq[M];
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+        mx[m] = -INFINITY;
+        sq[m] = 0.f;
+    }
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int i = lane; i < HW; i += 64) {
+        float p[M];
+#pragma unroll
+        for (int m = 0; m < M; ++m) p[m] = a[m * sm + i];
+        float t = p[0];
+#pragma unroll
+        for (int m = 1; m < M; ++m) t += p[m];
+        t /= (float)M;
+        if (mo != nullptr) mo[i] = t;
+        if (beats(t, i, bv, bi)) {
+            bv = t;
+            bi = i;
+        }
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+            mx[m] = nanmax(mx[m], p[m]);
+            const float d = p[m] - t;
+            sq[m] += d * d;
+        }
+    }
+#pragma unroll
+    for (int m = 0; m < M; ++m)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            mx[m] = nanmax(mx[m], __shfl_xor(mx[m], o, 64));
+            sq[m] += __shfl_xor(sq[m], o, 64);
+        }
+    const float es = finish_map(bv, bi, lane, map, W, tinv, K, ens_raw, ens_preds, ens_score);
+    if (lane != 0) return;
+    const float th = thr[0];
+    const bool eok = es >= th;                                      // :190-193 (a NaN never selects)
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+        const int64_t o = (int64_t)m * maps + map;
+        if (member_score) member_score[o] = mx[m];
+        if (disagree) disagree[o] = sq[m] / (float)HW;               // :184
+        select[o] = (mx[m] >= th && eok) ? 1.f : 0.f;                // :187-189
+    }
+}
+
+template <int M>
+void launch_ensemble_pseudo(hipStream_t st, const float* hm, int64_t sm, int64_t sb, int maps, int H, int W,
+                            const double* tinv, int K, const float* thr, float* mean_hm, float* ens_raw,
+                            float* ens_preds, float* ens_score, float* member_score, float* disagree,
+                            float* select) {
+    hipLaunchKernelGGL(ensemble_pseudo_kernel<M>, dim3(ubpl::cdiv(maps, 4)), dim3(256), 0, st, hm, sm, sb, maps, H, W,
+                       tinv, K, thr, mean_hm, ens_raw, ens_preds, ens_score, member_score, disagree, select);
 }
 
 // PCK (utils/evaluation.py:91-139).  One workgroup; thread per keypoint.
@@ -204,6 +289,27 @@ UBPL_API int ubpl_decode_heatmaps_flip(const float* hm, const float* hm_flip, in
     else
         hipLaunchKernelGGL(argmax_flip_kernel<false>, dim3(ubpl::cdiv(maps, 4)), dim3(256), 0, (hipStream_t)stream,
                            hm, hm_flip, sb, maps, H, W, perm, tinv, K, merged, raw, preds, scores);
+    UBPL_LAUNCH_CHECK();
+    return 0;
+}
+
+// Ensemble pseudo-labels (see include/ubpl_hip.h): member m's map (n, k) at hm + m*sm + n*sb + k*H*W.
+UBPL_API int ubpl_ensemble_pseudo(const float* hm, int64_t sm, int64_t sb, int M, int N, int K, int H, int W,
+                                  const double* tinv, const float* thr, float* mean_hm, float* ens_raw,
+                                  float* ens_preds, float* ens_score, float* member_score, float* disagree,
+                                  float* select, void* stream) {
+    if (M < 1 || M > 8 || N < 0 || K < 1 || H < 1 || W < 1 || (int64_t)H * W > 0x7fffffff ||
+        (int64_t)N * K > 0x3fffffff || (N > 1 && sb < (int64_t)K * H * W) || (M > 1 && sm < (int64_t)K * H * W) ||
+        (ens_preds != nullptr && tinv == nullptr) || hm == nullptr || thr == nullptr || select == nullptr)
+        return (int)hipErrorInvalidValue;
+    const int maps = N * K;
+    if (maps == 0) return 0;
+    // one instantiation per member count: the M values of a pixel stay in registers
+    static constexpr decltype(&launch_ensemble_pseudo<1>) by_members[8] = {
+        launch_ensemble_pseudo<1>, launch_ensemble_pseudo<2>, launch_ensemble_pseudo<3>, launch_ensemble_pseudo<4>,
+        launch_ensemble_pseudo<5>, launch_ensemble_pseudo<6>, launch_ensemble_pseudo<7>, launch_ensemble_pseudo<8>};
+    by_members[M - 1]((hipStream_t)stream, hm, sm, sb, maps, H, W, tinv, K, thr, mean_hm, ens_raw, ens_preds, ens_score,
+                      member_score, disagree, select);
     UBPL_LAUNCH_CHECK();
     return 0;
 }

@@ -33,6 +33,7 @@ SIGNATURES = {
     "ubpl_fdl_cov_backward": (I, [P, P, P, P, P, P, P, P, I, I, I, I, P, P, I, P]),
     "ubpl_decode_heatmaps": (I, [P, I, I, I, I, P, P, P, P, P]),
     "ubpl_decode_heatmaps_flip": (I, [P, P, L, I, I, I, I, P, P, P, P, P, P, P]),
+    "ubpl_ensemble_pseudo": (I, [P, L, L, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P]),
     "ubpl_pck": (I, [P, P, I, I, I, I, F, P, P, P, P, P]),
     "ubpl_ema_update": (I, [P, P, L, D, P]),
     "ubpl_adamw_step": (I, [P, P, P, P, L, D, D, D, D, D, L, P]),

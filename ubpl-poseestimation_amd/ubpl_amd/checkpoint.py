@@ -9,6 +9,7 @@ to checkpoint_best.pth.tar when is_best); save_checkpoint below does the same
 for callers without the reference tree.  Loading uses torch.load(...,
 weights_only=True): a checkpoint is tensors, numbers and lists only.
 """
+import json
 import os
 import shutil
 
@@ -48,6 +49,28 @@ def save_checkpoint(state, is_best, ckpt_path="ckpts"):
     if is_best:
         shutil.copyfile(path, os.path.join(ckpt_path, "checkpoint_best.pth.tar"))
     return path
+
+
+def save_pseudo_data(d, path):
+    """Write a Predictor.label_pool result as JSON.  It keeps the reference's
+    predsArraies key (projects/MT_UBPL.py:119-121, the per-epoch dump of the
+    networks' predictions) and adds what the reference leaves out: the
+    selection, its threshold and rule, and the confidence figures."""
+    if "predsArraies" not in d:
+        raise ValueError("ubpl_amd: pseudo data carries the predsArraies key")
+    parent = os.path.dirname(os.path.abspath(path))
+    os.makedirs(parent, exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(d, f)
+    return path
+
+
+def load_pseudo_data(path):
+    with open(path) as f:
+        d = json.load(f)
+    if "predsArraies" not in d:
+        raise ValueError("ubpl_amd: %s holds no predsArraies" % path)
+    return d
 
 
 def load_checkpoint(path, models, models_ema, optims, map_location=None):

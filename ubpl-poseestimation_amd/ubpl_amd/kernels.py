@@ -212,6 +212,44 @@ def decode_heatmaps_flip(hm, hm_flip, sb, N, K, H, W, perm=None, tinv=None, want
     return raw, preds, scores, merged
 
 
+def ensemble_pseudo(hm, sm, sb, M, N, K, H, W, thr, tinv=None, want_mean=False, out=None):
+    """UBPL ensemble pseudo-labels (ubpl_ensemble_pseudo; JointPseudoLoss3's target and
+    mask, utils/losses.py:176-210): hm is a tensor whose first element is member 0's map
+    (0, 0), member stride sm and batch stride sb floats — a [M,N,K,H,W] buffer, or the last
+    stacks of [M,B,S,K,H,W] through a view at an element offset.  1 <= M <= 8.  thr: device
+    float32 [1] (read by the kernel).
+    -> (ens_raw [N,K,2], ens_preds [N,K,2] or None, ens_score [N,K], member_score [M,N,K],
+        disagree [M,N,K], select [M,N,K] 0/1, mean_hm [N,K,H,W] or None);
+    out = the same tuple: write into these instead of allocating (select is required)."""
+    if not 1 <= M <= 8:
+        raise ValueError("ubpl_amd: ensemble_pseudo takes 1 to 8 members, got %d" % M)
+    _chk(hm, "hm")
+    need = (M - 1) * sm + (N - 1) * sb + K * H * W
+    if hm.numel() < need:
+        raise ValueError("ubpl_amd: hm holds %d floats, %d x %d maps of strides %d, %d need %d"
+                         % (hm.numel(), M, N, sm, sb, need))
+    _chk(thr, "thr")
+    _chk(tinv, "tinv", torch.float64)
+    if thr is None or thr.numel() != 1:
+        raise ValueError("ubpl_amd: thr is a device float32 tensor of one element")
+    dev = hm.device
+    if out is not None:
+        ens_raw, ens_preds, ens_score, member_score, disagree, select, mean_hm = out
+    else:
+        ens_raw = torch.empty((N, K, 2), device=dev, dtype=F32)
+        ens_preds = torch.empty((N, K, 2), device=dev, dtype=F32) if tinv is not None else None
+        ens_score = torch.empty((N, K), device=dev, dtype=F32)
+        member_score = torch.empty((M, N, K), device=dev, dtype=F32)
+        disagree = torch.empty((M, N, K), device=dev, dtype=F32)
+        select = torch.empty((M, N, K), device=dev, dtype=F32)
+        mean_hm = torch.empty((N, K, H, W), device=dev, dtype=F32) if want_mean else None
+    if select is None:
+        raise ValueError("ubpl_amd: ensemble_pseudo always writes select")
+    call("ubpl_ensemble_pseudo", _p(hm), int(sm), int(sb), M, N, K, H, W, _p(tinv), _p(thr), _p(mean_hm),
+         _p(ens_raw), _p(ens_preds), _p(ens_score), _p(member_score), _p(disagree), _p(select))
+    return ens_raw, ens_preds, ens_score, member_score, disagree, select, mean_hm
+
+
 def fliplr(x, out=None):
     """ProcessUtils.image_fliplr on device planes: x [..., H, W] -> x mirrored along W
     (out: a different tensor of x's size)."""

@@ -20,6 +20,12 @@ Three things make it cheap at small batches:
   the mean are captured in one HIP graph on ONE stream (several networks run
   one after another: no fork inside the capture) and replayed.
 
+`Predictor.pseudo_label` asks the method's own question of unlabeled images:
+which joints do the networks agree on confidently enough to use as labels
+(JointPseudoLoss3's target and mask, utils/losses.py:176-210)?  It is the
+same replay with one more launch, ubpl_ensemble_pseudo, over the networks'
+merged heatmaps; `label_pool` runs it over a loader.
+
 There is no CPU fallback.
 """
 import os
@@ -53,6 +59,39 @@ class _Slot:
         if self.graph is not None:
             self.graph.reset()
             self.graph = None
+
+
+class _PseudoSlot(_Slot):
+    """A slot of pseudo_label: predict's buffers with the merged heatmaps always kept
+    (the ensemble kernel reads them in place), the ensemble outputs and the threshold.
+    One slot serves calls with and without return_heatmaps."""
+
+    def __init__(self, M, N, K, R, flip, dev):
+        super().__init__(M, N, K, R, flip, True, dev)
+        f32 = dict(device=dev, dtype=torch.float32)
+        self.thr = torch.zeros(1, **f32)
+        self.ens_raw = torch.zeros((N, K, 2), **f32)
+        self.ens_preds = torch.zeros((N, K, 2), **f32)
+        self.ens_score = torch.zeros((N, K), **f32)
+        self.disagree = torch.zeros((M, N, K), **f32)
+        self.select = torch.zeros((M, N, K), **f32)
+        self.spread = torch.zeros((N, K), **f32)
+        self.mean_hm = torch.zeros((N, K, self.H, self.W), **f32)
+
+
+RULES = ("unanimous", "ensemble")
+
+
+def check_rule(rule):
+    if rule not in RULES:
+        raise ValueError("ubpl_amd: rule is one of %s, got %r" % (", ".join(RULES), rule))
+    return rule
+
+
+def assemble_kps(ens_preds, selected):
+    """[N,K,2] image coordinates + [N,K] bool -> [N,K,3] (x, y, selected as 0/1), the
+    meta["kpsMap"] layout."""
+    return torch.cat([ens_preds, selected.to(ens_preds.dtype).unsqueeze(-1)], -1)
 
 
 class Predictor:
@@ -138,8 +177,9 @@ class Predictor:
                                          s.heatmaps[mi] if s.heatmaps is not None else None))
         s.mean.copy_(torch.stack(list(s.preds), -1).mean(-1))       # projects/MT_UBPL.py:387
 
-    def _slot(self, N, R, want_hm):
-        key = (N, R, want_hm)
+    def _slot(self, N, R, want_hm, pseudo=False):
+        # (pseudo_label's slots carry a key of their own: predict's graphs and buffers stay its own)
+        key = ("pseudo", N, R) if pseudo else (N, R, want_hm)
         s = self._slots.get(key)
         if s is not None:
             self._slots.move_to_end(key)
@@ -149,8 +189,25 @@ class Predictor:
             old.release()
             del old
             torch.cuda.empty_cache()
-        s = self._slots[key] = _Slot(len(self.models), N, self.k, R, self.flip_test, want_hm, self.device)
+        a = (len(self.models), N, self.k, R, self.flip_test)
+        s = self._slots[key] = _PseudoSlot(*a, self.device) if pseudo else _Slot(*a, want_hm, self.device)
         return s, True
+
+    def _launch(self, s, new, run):
+        """run(s) eagerly, or captured once per slot and replayed."""
+        if not self.use_graph:
+            run(s)
+            return
+        if new:
+            # warm-up: the networks' per-batch-size scratch is allocated here, outside the
+            # graph's pool; then the capture (which records, it does not execute)
+            run(s)
+            torch.cuda.synchronize(self.device)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                run(s)
+            s.graph = g
+        s.graph.replay()
 
     def _predict_chunk(self, imgs, tinv, want_hm):
         N, R = imgs.shape[0], imgs.shape[2]
@@ -158,19 +215,7 @@ class Predictor:
         s.imgs.copy_(imgs, non_blocking=True)
         if tinv is not None:
             s.tinv.copy_(tinv, non_blocking=True)
-        if not self.use_graph:
-            self._run(s)
-        else:
-            if new:
-                # warm-up: the networks' per-batch-size scratch is allocated here, outside the
-                # graph's pool; then the capture (which records, it does not execute)
-                self._run(s)
-                torch.cuda.synchronize(self.device)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._run(s)
-                s.graph = g
-            s.graph.replay()
+        self._launch(s, new, self._run)
         out = {"raw": s.raw.clone(), "scores": s.scores.clone(),
                "preds": s.preds.clone() if tinv is not None else None,
                "preds_mean": s.mean.clone() if tinv is not None else None}
@@ -178,15 +223,11 @@ class Predictor:
             out["heatmaps"] = s.heatmaps.clone()
         return out
 
-    def predict(self, imgs, center=None, scale=None, return_heatmaps=False, out_res=None):
-        """imgs float32 [N,3,R,R] (host or device) -> dict of device tensors, the caller's own:
-        raw [M,N,K,2] 1-based heatmap coordinates, scores [M,N,K], preds [M,N,K,2] and
-        preds_mean [N,K,2] in image coordinates (None without center / scale), and with
-        return_heatmaps heatmaps [M,N,K,H,W], the (flip-merged) last-stack maps; M networks.
-        out_res: the resolution of the inverse transform (default: the heatmaps')."""
+    def _inputs(self, what, imgs, center, scale, out_res):
+        """The argument checks of predict / pseudo_label -> (contiguous images, tinv or None)."""
         if not torch.is_tensor(imgs) or imgs.dtype != torch.float32 or imgs.dim() != 4 or imgs.shape[1] != 3 \
                 or imgs.shape[2] != imgs.shape[3] or imgs.shape[0] < 1:
-            raise TypeError("ubpl_amd: predict takes float32 images [N,3,R,R], N >= 1")
+            raise TypeError("ubpl_amd: %s takes float32 images [N,3,R,R], N >= 1" % what)
         if (center is None) != (scale is None):
             raise ValueError("ubpl_amd: center and scale come together")
         N, R = imgs.shape[0], imgs.shape[2]
@@ -197,7 +238,16 @@ class Predictor:
             tinv = inverse_transforms(center, scale, res)
             if tinv.shape[0] != N:
                 raise ValueError("ubpl_amd: %d centers for %d images" % (tinv.shape[0], N))
-        imgs = imgs.contiguous()
+        return imgs.contiguous(), tinv
+
+    def predict(self, imgs, center=None, scale=None, return_heatmaps=False, out_res=None):
+        """imgs float32 [N,3,R,R] (host or device) -> dict of device tensors, the caller's own:
+        raw [M,N,K,2] 1-based heatmap coordinates, scores [M,N,K], preds [M,N,K,2] and
+        preds_mean [N,K,2] in image coordinates (None without center / scale), and with
+        return_heatmaps heatmaps [M,N,K,H,W], the (flip-merged) last-stack maps; M networks.
+        out_res: the resolution of the inverse transform (default: the heatmaps')."""
+        imgs, tinv = self._inputs("predict", imgs, center, scale, out_res)
+        N = imgs.shape[0]
         outs = []
         with torch.cuda.device(self.device), torch.no_grad():
             for a in range(0, N, self.max_batch):
@@ -207,6 +257,105 @@ class Predictor:
             return outs[0]
         return {k: None if outs[0][k] is None else torch.cat([o[k] for o in outs], 0 if k == "preds_mean" else 1)
                 for k in outs[0]}
+
+    # -- ensemble pseudo-labels --------------------------------------------
+    def _run_pseudo(self, s):
+        """_run, then the ensemble kernel on the merged heatmaps it left in s.heatmaps
+        (the members' peaks are s.scores already: not written again) and the members'
+        spread around the ensemble peak."""
+        self._run(s)
+        M, N, K, H, W = len(self.models), s.N, self.k, s.H, s.W
+        Kn.ensemble_pseudo(s.heatmaps, N * K * H * W, K * H * W, M, N, K, H, W, s.thr, s.tinv,
+                           out=(s.ens_raw, s.ens_preds, s.ens_score, None, s.disagree, s.select,
+                                s.mean_hm))
+        d = s.raw - s.ens_raw
+        s.spread.copy_((d * d).sum(-1).sqrt().amax(0))
+
+    def _pseudo_chunk(self, imgs, tinv, thr, rule, want_hm):
+        N, R = imgs.shape[0], imgs.shape[2]
+        s, new = self._slot(N, R, True, pseudo=True)
+        s.imgs.copy_(imgs, non_blocking=True)
+        if tinv is not None:
+            s.tinv.copy_(tinv, non_blocking=True)
+        s.thr.fill_(thr)                                            # read by the kernel at replay
+        self._launch(s, new, self._run_pseudo)
+        have = tinv is not None
+        select = s.select > 0
+        selected = select.all(0) if rule == "unanimous" else s.ens_score >= s.thr
+        out = {"raw": s.raw.clone(), "scores": s.scores.clone(),
+               "preds": s.preds.clone() if have else None,
+               "preds_mean": s.mean.clone() if have else None,
+               "ens_raw": s.ens_raw.clone(), "ens_preds": s.ens_preds.clone() if have else None,
+               "ens_score": s.ens_score.clone(), "member_select": select, "disagree": s.disagree.clone(),
+               "selected": selected, "spread": s.spread.clone(),
+               "kps": assemble_kps(s.ens_preds, selected) if have else None}
+        if want_hm:
+            out["heatmaps"] = s.heatmaps.clone()
+            out["mean_heatmap"] = s.mean_hm.clone()
+        return out
+
+    _PER_MEMBER = ("raw", "scores", "preds", "member_select", "disagree", "heatmaps")
+
+    def pseudo_label(self, imgs, center=None, scale=None, thr=0.95, rule="unanimous", return_heatmaps=False,
+                     out_res=None):
+        """The UBPL ensemble pseudo-labels of imgs (JointPseudoLoss3's target and mask,
+        utils/losses.py:176-210, with every network in the student's place in turn): which
+        joints do the networks agree on confidently enough to use as labels?  Same inputs,
+        forwards, flip test and chunking as predict.  -> dict of device tensors, the caller's
+        own: everything predict returns, and
+          ens_raw [N,K,2], ens_score [N,K]   the decode of T, the per-pixel mean of the M
+                                             networks' heatmaps (:179);
+          ens_preds [N,K,2]                  ens_raw in image coordinates (None without center / scale);
+          member_select [M,N,K] bool         max_px p_m >= thr and ens_score >= thr (:187-193);
+          disagree [M,N,K]                   mean_px (p_m - T)^2 (:184);
+          selected [N,K] bool                rule "unanimous": every member selects;
+                                             rule "ensemble": ens_score >= thr alone;
+          spread [N,K]                       max over m of |raw[m] - ens_raw|, heatmap pixels;
+          kps [N,K,3]                        (ens_preds x, y, selected as 0/1), the meta["kpsMap"]
+                                             layout (None without center / scale);
+        with return_heatmaps, heatmaps [M,N,K,H,W] and mean_heatmap [N,K,H,W] (T).
+        thr defaults to the reference's pseudoScoreThr; one captured graph serves every thr."""
+        check_rule(rule)
+        if len(self.models) > 8:
+            raise ValueError("ubpl_amd: pseudo_label takes up to 8 networks, got %d" % len(self.models))
+        imgs, tinv = self._inputs("pseudo_label", imgs, center, scale, out_res)
+        N = imgs.shape[0]
+        outs = []
+        with torch.cuda.device(self.device), torch.no_grad():
+            for a in range(0, N, self.max_batch):
+                b = min(N, a + self.max_batch)
+                outs.append(self._pseudo_chunk(imgs[a:b], None if tinv is None else tinv[a:b], float(thr), rule,
+                                               bool(return_heatmaps)))
+        if len(outs) == 1:
+            return outs[0]
+        return {k: None if outs[0][k] is None else torch.cat([o[k] for o in outs], 1 if k in self._PER_MEMBER else 0)
+                for k in outs[0]}
+
+    def label_pool(self, loader, args=None, thr=0.95, rule="unanimous"):
+        """pseudo_label over a loader of (imgMap, _, meta) batches with meta["center"] /
+        meta["scale"] (the shape validate takes; args.outRes, when given, is the resolution of
+        the inverse transform).  -> a host dict of plain lists, sample-major: predsArraies
+        (the reference's key, projects/MT_UBPL.py:120: [x, y] per joint from ens_preds),
+        selected, ens_score, spread [N][K], disagree [N][M][K], thr, rule and
+        selected_fraction [K].  Single process only, as validate."""
+        from . import dist as D
+        if D.is_dist():
+            raise NotImplementedError("ubpl_amd: Predictor.label_pool runs in one process")
+        check_rule(rule)
+        keys = ("ens_preds", "selected", "ens_score", "spread", "disagree")
+        cols = {k: [] for k in keys}
+        for imgMap, _, meta in loader:
+            out = self.pseudo_label(imgMap.float(), meta["center"], meta["scale"], thr=thr, rule=rule,
+                                    out_res=None if args is None else args.outRes)
+            out["disagree"] = out["disagree"].transpose(0, 1)
+            for k in keys:
+                cols[k].append(out[k].cpu())
+        cat = {k: torch.cat(v) if v else torch.zeros(0) for k, v in cols.items()}
+        sel = cat["selected"]
+        return {"predsArraies": cat["ens_preds"].tolist(), "selected": sel.tolist(),
+                "ens_score": cat["ens_score"].tolist(), "spread": cat["spread"].tolist(),
+                "disagree": cat["disagree"].tolist(), "thr": float(thr), "rule": rule,
+                "selected_fraction": sel.float().mean(0).tolist() if sel.numel() else []}
 
     def validate(self, loader, args):
         """train.validate(loader, models, args) from the frozen snapshot: the same triple
