@@ -17,10 +17,18 @@
  * before a declaration gives each pointer argument its element type (f32,
  * f64, i32, i64, u16 = bf16 pieces, u8) and the number of elements the call
  * may touch, as a C expression of the integer arguments ("?" = not derivable
- * from them).  csrc/gen_torch_ops.py turns them into the torch ops' argument
- * checks (dtype, contiguity, storage extent), so a short tensor raises there
- * instead of being written out of bounds.  The Python host layer (ubpl-poseestimation_amd/ubpl_amd)
- * binds these through ctypes and re-exposes the reference's module API.
+ * from them).
+ *
+ * This header is the only description of the ABI.  Its one parser,
+ * ubpl-poseestimation_amd/ubpl_amd/_abi.py, derives both bindings from it: the
+ * build generates the torch ops (one per entry; the annotations become their
+ * argument checks of dtype, contiguity and storage extent, so a short tensor
+ * raises there instead of being written out of bounds), through which the
+ * Python host layer (ubpl-poseestimation_amd/ubpl_amd) makes every launch and
+ * re-exposes the reference's module API; and the library loader builds the
+ * ctypes signatures used for the host-only queries and the ABI tests.  The
+ * parser reads declarations that start a line with their return type (int or
+ * int64_t) and take int, int64_t, float, double and pointer parameters.
  */
 #ifndef UBPL_HIP_H
 #define UBPL_HIP_H

@@ -31,6 +31,51 @@ def test_library_exports_every_header_symbol():
     for s in syms:
         assert hasattr(lib, s), s
     assert set(syms) == set(_lib.SIGNATURES), set(syms) ^ set(_lib.SIGNATURES)
+    # the ctypes signatures are derived from the header: anchors written out by hand (a host-only
+    # query with an int64 return, a double among pointers, a float after an int64 count)
+    from ctypes import c_double as D, c_float as F, c_int as I, c_int64 as L, c_void_p as P
+    assert _lib.SIGNATURES["ubpl_bn_partial_floats"] == (L, [I, L])
+    assert _lib.SIGNATURES["ubpl_ema_update"] == (I, [P, P, L, D, P])
+    assert _lib.SIGNATURES["ubpl_scale_"] == (I, [P, L, F, P])
+    assert lib.ubpl_scale_.argtypes == [P, L, F, P] and lib.ubpl_bn_partial_floats.restype is L
+
+
+_HEADER_TEXT = """
+/* A comment that looks like an entry must not become one:
+int ubpl_in_a_comment(const float* x, int n, void* stream);
+ */
+/*@ x:f32[(int64_t)B*n] out:i32[B] */
+int ubpl_three_lines(const float* x, int B,
+                     int64_t n, float eps,
+                     double alpha, int* out, void* stream);
+/* host-only: no stream, returns a size */
+int64_t ubpl_three_lines_workspace(int B, int64_t n);
+"""
+
+
+def test_header_parser_on_a_text():
+    """ubpl_amd._abi.parse — the one parser both bindings come from — on a header held here:
+    a declaration over three lines, a declaration-shaped comment, a host-only entry, and the
+    two things it refuses (each naming the entry)."""
+    from ubpl_amd import _abi
+    decls = _abi.parse(_HEADER_TEXT)
+    assert [d[:2] for d in decls] == [("int", "ubpl_three_lines"), ("int64_t", "ubpl_three_lines_workspace")]
+    assert decls[0][2] == [("const float*", "x"), ("int", "B"), ("int64_t", "n"), ("float", "eps"),
+                           ("double", "alpha"), ("int*", "out"), ("void*", "stream")]
+    assert decls[0][3] == {"x": ("f32", "(int64_t)B*n"), "out": ("i32", "B")}
+    assert decls[1][2:] == ([("int", "B"), ("int64_t", "n")], {})
+    src = _abi.gen(decls)
+    assert 'm.def("three_lines(Tensor? x, int B, int n, float eps, float alpha, Tensor(a0!)? out) -> ()");' in src
+    assert 'm.def("three_lines_workspace(int B, int n) -> int");' in src
+    assert 'chk(x, "three_lines", "x", {at::kFloat}, "f32", (int64_t)((int64_t)B*n));' in src
+    assert "in_a_comment" not in src
+    with pytest.raises(ValueError, match="ubpl_bare.*y"):          # a device pointer without an annotation
+        _abi.parse("/*@ x:f32[n] */\nint ubpl_bare(const float* x, float* y, int n, void* stream);\n")
+    with pytest.raises(ValueError, match="size_t.*ubpl_wide"):     # a scalar type the bindings do not map
+        _abi.parse("/*@ x:f32[n] */\nint ubpl_wide(const float* x, size_t n, void* stream);\n")
+    from ubpl_amd import _lib
+    with pytest.raises(RuntimeError, match="no_such_dir/ubpl_hip.h not found"):   # like a missing library
+        _lib.signatures("no_such_dir/ubpl_hip.h")
 
 
 def test_torch_ops_mirror_the_header():

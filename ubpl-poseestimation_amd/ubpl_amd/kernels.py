@@ -14,12 +14,6 @@ from ._lib import call
 F32 = torch.float32
 
 
-def _p(t):
-    """A device-pointer argument of a C-ABI entry: the tensor itself (its op
-    passes data_ptr()), or None for NULL."""
-    return t
-
-
 def _chk(t, name, dtype=F32):
     if t is None:
         return
@@ -40,8 +34,8 @@ def render_heatmaps(kps, img_hw, inp_res, out_res, kernel_size=3.0, sigma=1.0, c
     hm = torch.empty((N, K, rh, rw), device=kps.device, dtype=F32)
     if kps_out is None:
         kps_out = torch.empty_like(kps)
-    call("ubpl_render_heatmaps", _p(kps), _p(hm), _p(kps_out), N, K, int(img_hw[0]), int(img_hw[1]),
-         int(inp_res), int(out_res), float(kernel_size), float(sigma), float(cutoff))
+    call("ubpl_render_heatmaps", kps, hm, kps_out, N, K, int(img_hw[0]), int(img_hw[1]), int(inp_res), int(out_res),
+         float(kernel_size), float(sigma), float(cutoff))
     return hm, kps_out
 
 
@@ -97,8 +91,7 @@ def row_stats(g, want_amax=False, want_tmax=False):
     am = torch.empty(rows, device=dev, dtype=F32) if want_amax else None
     tm = torch.empty(rows, device=dev, dtype=F32) if want_tmax else None
     a_sb, a_ss, t_sb, t_ss, t_sm, M, B, S, K, HW = g.args
-    call("ubpl_heatmap_row_stats", g.a_ptr, a_sb, a_ss, g.t_ptr, t_sb, t_ss, t_sm, M, B, S, K, HW,
-         _p(sq), _p(am), _p(tm))
+    call("ubpl_heatmap_row_stats", g.a_ptr, a_sb, a_ss, g.t_ptr, t_sb, t_ss, t_sm, M, B, S, K, HW, sq, am, tm)
     return sq, am, tm
 
 
@@ -108,15 +101,15 @@ def loss_finalize(kind, sq, amax, tmax, gate, sw, use_gate, use_sw, B, S, K, thr
     out_cnt = torch.empty(4, device=dev, dtype=torch.int32)
     score = torch.empty(K, device=dev, dtype=F32) if kind != 0 else None
     w = torch.empty(B * S * K, device=dev, dtype=F32)
-    call("ubpl_loss_finalize", int(kind), _p(sq), _p(amax), _p(tmax), _p(gate), _p(sw), int(use_gate),
-         int(use_sw), B, S, K, float(thr), _p(out_sum), _p(out_cnt), _p(score), _p(w))
+    call("ubpl_loss_finalize", int(kind), sq, amax, tmax, gate, sw, int(use_gate), int(use_sw), B, S, K, float(thr),
+         out_sum, out_cnt, score, w)
     return out_sum, out_cnt, score, w
 
 
 def row_grad(g, w, gscale, extra, da, accumulate=False):
     a_sb, a_ss, t_sb, t_ss, t_sm, M, B, S, K, HW = g.args
-    call("ubpl_heatmap_row_grad", g.a_ptr, a_sb, a_ss, g.t_ptr, t_sb, t_ss, t_sm, M, B, S, K, HW, _p(w),
-         _p(gscale), float(extra), _p(da), int(accumulate))
+    call("ubpl_heatmap_row_grad", g.a_ptr, a_sb, a_ss, g.t_ptr, t_sb, t_ss, t_sm, M, B, S, K, HW, w, gscale,
+         float(extra), da, int(accumulate))
     return da
 
 
@@ -131,8 +124,7 @@ def fdl_cov_forward(f1, f2, rowmask=None):
     mu1, mu2 = torch.empty_like(cov), torch.empty_like(cov)
     val = torch.empty(1, device=dev, dtype=F32)
     cnt = torch.empty(1, device=dev, dtype=torch.int32)
-    call("ubpl_fdl_cov_forward", _p(f1), _p(f2), _p(rowmask), B, S, C, HW, _p(cov), _p(mu1), _p(mu2), _p(val),
-         _p(cnt))
+    call("ubpl_fdl_cov_forward", f1, f2, rowmask, B, S, C, HW, cov, mu1, mu2, val, cnt)
     return val, cnt, (cov, mu1, mu2)
 
 
@@ -140,8 +132,7 @@ def fdl_cov_backward(f1, f2, rowmask, saved, cnt, gscale, d1=None, d2=None, accu
     B, S, C = f1.shape[:3]
     HW = f1[0, 0, 0].numel()
     cov, mu1, mu2 = saved
-    call("ubpl_fdl_cov_backward", _p(f1), _p(f2), _p(rowmask), _p(cov), _p(mu1), _p(mu2), _p(cnt), _p(gscale),
-         B, S, C, HW, _p(d1), _p(d2), int(accumulate))
+    call("ubpl_fdl_cov_backward", f1, f2, rowmask, cov, mu1, mu2, cnt, gscale, B, S, C, HW, d1, d2, int(accumulate))
     return d1, d2
 
 
@@ -156,7 +147,7 @@ def decode_heatmaps(hm, tinv=None):
     scores = torch.empty((N, K), device=dev, dtype=F32)
     if tinv is not None:
         _chk(tinv, "tinv", torch.float64)
-    call("ubpl_decode_heatmaps", _p(hm), N, K, H, W, _p(tinv), _p(raw), _p(preds), _p(scores))
+    call("ubpl_decode_heatmaps", hm, N, K, H, W, tinv, raw, preds, scores)
     return raw, preds, scores
 
 
@@ -207,8 +198,7 @@ def decode_heatmaps_flip(hm, hm_flip, sb, N, K, H, W, perm=None, tinv=None, want
         preds = torch.empty((N, K, 2), device=dev, dtype=F32) if tinv is not None else None
         scores = torch.empty((N, K), device=dev, dtype=F32)
         merged = torch.empty((N, K, H, W), device=dev, dtype=F32) if want_merged else None
-    call("ubpl_decode_heatmaps_flip", _p(hm), _p(hm_flip), int(sb), N, K, H, W, _p(perm), _p(tinv), _p(merged),
-         _p(raw), _p(preds), _p(scores))
+    call("ubpl_decode_heatmaps_flip", hm, hm_flip, int(sb), N, K, H, W, perm, tinv, merged, raw, preds, scores)
     return raw, preds, scores, merged
 
 
@@ -245,8 +235,8 @@ def ensemble_pseudo(hm, sm, sb, M, N, K, H, W, thr, tinv=None, want_mean=False, 
         mean_hm = torch.empty((N, K, H, W), device=dev, dtype=F32) if want_mean else None
     if select is None:
         raise ValueError("ubpl_amd: ensemble_pseudo always writes select")
-    call("ubpl_ensemble_pseudo", _p(hm), int(sm), int(sb), M, N, K, H, W, _p(tinv), _p(thr), _p(mean_hm),
-         _p(ens_raw), _p(ens_preds), _p(ens_score), _p(member_score), _p(disagree), _p(select))
+    call("ubpl_ensemble_pseudo", hm, int(sm), int(sb), M, N, K, H, W, tinv, thr, mean_hm, ens_raw, ens_preds, ens_score,
+         member_score, disagree, select)
     return ens_raw, ens_preds, ens_score, member_score, disagree, select, mean_hm
 
 
@@ -259,7 +249,7 @@ def fliplr(x, out=None):
     if y.numel() != x.numel() or y.data_ptr() == x.data_ptr():
         raise ValueError("ubpl_amd: fliplr writes a different tensor of the input's size")
     H, W = x.shape[-2], x.shape[-1]
-    call("ubpl_fliplr", _p(x), x.numel() // max(H * W, 1), H, W, _p(y))
+    call("ubpl_fliplr", x, x.numel() // max(H * W, 1), H, W, y)
     return y
 
 
@@ -272,8 +262,7 @@ def pck(preds, gts, ref, thr):
     accs = torch.empty(K + 1, device=dev, dtype=F32)
     hits = torch.empty(K, device=dev, dtype=torch.int32)
     valid = torch.empty(K, device=dev, dtype=torch.int32)
-    call("ubpl_pck", _p(preds), _p(gts), N, K, int(ref[0]), int(ref[1]), float(thr), _p(errs), _p(accs), _p(hits),
-         _p(valid))
+    call("ubpl_pck", preds, gts, N, K, int(ref[0]), int(ref[1]), float(thr), errs, accs, hits, valid)
     return errs, accs, hits, valid
 
 
@@ -282,34 +271,34 @@ def ema_update_(ema, p, alpha):
     _chk(ema, "ema")
     _chk(p, "param")
     assert ema.numel() == p.numel()
-    call("ubpl_ema_update", _p(ema), _p(p), ema.numel(), float(alpha))
+    call("ubpl_ema_update", ema, p, ema.numel(), float(alpha))
 
 
 def adamw_step_(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step):
     for t, n in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):
         _chk(t, n)
-    call("ubpl_adamw_step", _p(p), _p(g), _p(m), _p(v), p.numel(), float(lr), float(beta1), float(beta2),
-         float(eps), float(weight_decay), int(step))
+    call("ubpl_adamw_step", p, g, m, v, p.numel(), float(lr), float(beta1), float(beta2), float(eps),
+         float(weight_decay), int(step))
 
 
 
 def adamw_step_dev_(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step_t, coef):
     """AdamW with the step count in device memory (int64 scalar, incremented);
     replayable inside a captured HIP graph.  coef: 4-float scratch."""
-    call("ubpl_adamw_step_dev", _p(p), _p(g), _p(m), _p(v), p.numel(), float(lr), float(beta1), float(beta2),
-         float(eps), float(weight_decay), _p(step_t), _p(coef))
+    call("ubpl_adamw_step_dev", p, g, m, v, p.numel(), float(lr), float(beta1), float(beta2), float(eps),
+         float(weight_decay), step_t, coef)
 
 def adamw_ema_step_dev_(p, g, m, v, nlive, lr, beta1, beta2, eps, weight_decay, step_t, coef, ema, alpha):
     """adamw_step_dev_ on p[:nlive] and ema_update_(ema, p, alpha) over all of p, one pass."""
     if ema.numel() != p.numel() or nlive > p.numel():
         raise ValueError("adamw_ema_step_dev_: ema / p / nlive sizes disagree")
-    call("ubpl_adamw_ema_step_dev", _p(p), _p(g), _p(m), _p(v), int(nlive), float(lr), float(beta1), float(beta2),
-         float(eps), float(weight_decay), _p(step_t), _p(coef), _p(ema), p.numel(), float(alpha))
+    call("ubpl_adamw_ema_step_dev", p, g, m, v, int(nlive), float(lr), float(beta1), float(beta2), float(eps),
+         float(weight_decay), step_t, coef, ema, p.numel(), float(alpha))
 
 
 def scale_(x, s):
     _chk(x, "x")
-    call("ubpl_scale_", _p(x), x.numel(), float(s))
+    call("ubpl_scale_", x, x.numel(), float(s))
 
 
 # ------------------------------------------------------------------ BN
@@ -325,13 +314,12 @@ def bn_part(B, C, device):
 def bn_forward_stats(x, gamma, beta, eps, momentum, rmean, rvar, part, mean, invstd, scale, shift):
     B, C = x.shape[:2]
     HW = x[0, 0].numel()
-    call("ubpl_bn_forward_stats", _p(x), B, C, HW, _p(gamma), _p(beta), float(eps), float(momentum), _p(rmean),
-         _p(rvar), _p(part), _p(mean), _p(invstd), _p(scale), _p(shift))
+    call("ubpl_bn_forward_stats", x, B, C, HW, gamma, beta, float(eps), float(momentum), rmean, rvar, part, mean,
+         invstd, scale, shift)
 
 
 def bn_eval_coeffs(gamma, beta, rmean, rvar, eps, scale, shift):
-    call("ubpl_bn_eval_coeffs", _p(gamma), _p(beta), _p(rmean), _p(rvar), float(eps), gamma.numel(), _p(scale),
-         _p(shift))
+    call("ubpl_bn_eval_coeffs", gamma, beta, rmean, rvar, float(eps), gamma.numel(), scale, shift)
 
 
 def bn_coeff_table(rows, n_params, n_stats, n_coef):
@@ -349,14 +337,14 @@ def bn_coeff_table(rows, n_params, n_stats, n_coef):
 
 def bn_eval_coeffs_table(params, stats, table, eps, coef):
     """scale | shift of every BatchNorm of `table` (bn_coeff_table(...).to(device)) in one launch."""
-    call("ubpl_bn_eval_coeffs_table", _p(params), _p(stats), _p(table), int(table.shape[0]), float(eps), _p(coef))
+    call("ubpl_bn_eval_coeffs_table", params, stats, table, int(table.shape[0]), float(eps), coef)
 
 
 def bn_apply(x, scale, shift, relu, out=None):
     B, C = x.shape[:2]
     HW = x[0, 0].numel()
     y = torch.empty_like(x) if out is None else out
-    call("ubpl_bn_apply", _p(x), B, C, HW, _p(scale), _p(shift), int(relu), _p(y))
+    call("ubpl_bn_apply", x, B, C, HW, scale, shift, int(relu), y)
     return y
 
 
@@ -366,13 +354,13 @@ def bn_partial_buffer(C, N, device):
 
 def bn_partials(y, part):
     B, C = y.shape[:2]
-    call("ubpl_bn_partials", _p(y), B, C, y[0, 0].numel(), _p(part))
+    call("ubpl_bn_partials", y, B, C, y[0, 0].numel(), part)
     return part
 
 
 def bn_stats_from_partials(part, C, N, gamma, beta, eps, momentum, rmean, rvar, mean, invstd, scale, shift_out):
-    call("ubpl_bn_stats_from_partials", _p(part), C, int(N), _p(gamma), _p(beta), float(eps), float(momentum),
-         _p(rmean), _p(rvar), _p(mean), _p(invstd), _p(scale), _p(shift_out))
+    call("ubpl_bn_stats_from_partials", part, C, int(N), gamma, beta, float(eps), float(momentum), rmean, rvar, mean,
+         invstd, scale, shift_out)
 
 
 def bn_backward_split(dz, x, gamma, mean, invstd, scale, shift, relu, scratch, coef, dgamma, dbeta, npieces, pad,
@@ -384,9 +372,8 @@ def bn_backward_split(dz, x, gamma, mean, invstd, scale, shift, relu, scratch, c
     B, C, H, W = x.shape
     plane = B * C * (H + 2 * pad) * (W + 2 * pad)
     out = torch.empty(npieces * plane, device=x.device, dtype=torch.int16)
-    call("ubpl_bn_backward_split", _p(dz), _p(x), B, C, H, W, _p(gamma), _p(mean), _p(invstd), _p(scale), _p(shift),
-         int(relu), _p(scratch), _p(part), _p(coef), _p(dgamma), _p(dbeta), int(pad), int(npieces), _p(out),
-         int(plane))
+    call("ubpl_bn_backward_split", dz, x, B, C, H, W, gamma, mean, invstd, scale, shift, int(relu), scratch, part, coef,
+         dgamma, dbeta, int(pad), int(npieces), out, int(plane))
     return SplitAct(out, plane, B, C, H, W, pad, npieces, coef[3 * C:3 * C + 1] if npieces == 2 else None)
 
 
@@ -398,8 +385,8 @@ def bn_backward(dz, x, gamma, mean, invstd, scale, shift, relu, scratch, coef, d
     B, C = x.shape[:2]
     HW = x[0, 0].numel()
     dx = dz if out is None else out
-    call("ubpl_bn_backward", _p(dz), _p(x), B, C, HW, _p(gamma), _p(mean), _p(invstd), _p(scale), _p(shift),
-         int(relu), _p(scratch), _p(part), _p(coef), _p(dgamma), _p(dbeta), _p(add1), _p(add2), _p(dx))
+    call("ubpl_bn_backward", dz, x, B, C, HW, gamma, mean, invstd, scale, shift, int(relu), scratch, part, coef, dgamma,
+         dbeta, add1, add2, dx)
     return dx
 
 
@@ -408,11 +395,22 @@ def bn_bwd_partials(dz, x, scale, shift, mean, relu):
     B, C = x.shape[:2]
     HW = x[0, 0].numel()
     part = bn_partial_buffer(C, B * HW, x.device)
-    call("ubpl_bn_backward_partials", _p(dz), _p(x), B, C, HW, _p(scale), _p(shift), _p(mean), int(relu), _p(part))
+    call("ubpl_bn_backward_partials", dz, x, B, C, HW, scale, shift, mean, int(relu), part)
     return part
 
 
 # ------------------------------------------------------------------ conv
+def _workspace(query, *sizes):
+    """Floats of workspace the C-ABI size query `query` (a ubpl_*_workspace entry) asks for."""
+    return int(getattr(_lib.lib(), query)(*sizes))
+
+
+def _slab(query, device, *sizes, or_none=False):
+    """The f32 workspace slab of _workspace(query, *sizes) floats (or_none: None when it asks for none)."""
+    n = _workspace(query, *sizes)
+    return None if or_none and n <= 0 else torch.empty(n, device=device, dtype=F32)
+
+
 def conv_out_hw(H, W, KS, stride):
     pad = (KS - 1) // 2
     return (H + 2 * pad - KS) // stride + 1, (W + 2 * pad - KS) // stride + 1
@@ -421,7 +419,7 @@ def conv_out_hw(H, W, KS, stride):
 def conv_weight_tapmajor(w):
     Cout, Cin, KS, _ = w.shape
     wt = torch.empty((Cout, KS * KS, Cin), device=w.device, dtype=F32)
-    call("ubpl_conv_weight_tapmajor", _p(w), Cout, Cin, KS, _p(wt))
+    call("ubpl_conv_weight_tapmajor", w, Cout, Cin, KS, wt)
     return wt
 
 
@@ -441,10 +439,8 @@ def conv2d_forward(x, w, bias, stride=1, pscale=None, pshift=None, res=None, out
         raise AssertionError("{} {}".format(Cin, wc))  # models/base/layers.py:44
     Ho, Wo = conv_out_hw(H, W, KS, stride)
     y = torch.empty((B, Cout, Ho, Wo), device=x.device, dtype=F32) if out is None else out
-    nws = _lib.lib().ubpl_conv2d_forward_workspace(B, Cin, Cout, KS, Ho, Wo)
-    slab = torch.empty(int(nws), device=x.device, dtype=F32) if nws > 0 else None
-    call("ubpl_conv2d_forward", _p(x), B, Cin, H, W, _p(wk), _p(bias), Cout, KS, stride, _p(pscale), _p(pshift),
-         _p(res), _p(y), Ho, Wo, _p(slab))
+    slab = _slab("ubpl_conv2d_forward_workspace", x.device, B, Cin, Cout, KS, Ho, Wo, or_none=True)
+    call("ubpl_conv2d_forward", x, B, Cin, H, W, wk, bias, Cout, KS, stride, pscale, pshift, res, y, Ho, Wo, slab)
     return y
 
 
@@ -461,26 +457,23 @@ def conv1x1_forward_kmajor(x, wk, bias, pscale=None, pshift=None, res=None, out=
     B, Cin, H, W = x.shape
     Cout = wk.numel() // Cin
     y = torch.empty((B, Cout, H, W), device=x.device, dtype=F32) if out is None else out
-    nws = _lib.lib().ubpl_conv1x1_kmajor_workspace(B, Cin, Cout, H * W)
-    slab = torch.empty(int(nws), device=x.device, dtype=F32) if nws > 0 else None
-    call("ubpl_conv1x1_forward_kmajor", _p(x), B, Cin, H * W, _p(wk), _p(bias), Cout, _p(pscale), _p(pshift),
-         _p(res), _p(y), _p(slab), _p(stat_part))
+    slab = _slab("ubpl_conv1x1_kmajor_workspace", x.device, B, Cin, Cout, H * W, or_none=True)
+    call("ubpl_conv1x1_forward_kmajor", x, B, Cin, H * W, wk, bias, Cout, pscale, pshift, res, y, slab, stat_part)
     return y
 
 
 def conv2d_wgrad(dy, x, KS, stride, dw, db, pscale=None, pshift=None, accumulate=True):
     B, Cin, H, W = x.shape
     Cout, Ho, Wo = dy.shape[1], dy.shape[2], dy.shape[3]
-    n = _lib.lib().ubpl_conv2d_wgrad_workspace(B, Cin, Cout, KS, Ho, Wo)
-    slab = torch.empty(int(n), device=x.device, dtype=F32)
-    call("ubpl_conv2d_wgrad", _p(dy), _p(x), B, Cin, H, W, Cout, KS, stride, _p(pscale), _p(pshift), Ho, Wo,
-         _p(slab), _p(dw), _p(db), int(accumulate))
+    slab = _slab("ubpl_conv2d_wgrad_workspace", x.device, B, Cin, Cout, KS, Ho, Wo)
+    call("ubpl_conv2d_wgrad", dy, x, B, Cin, H, W, Cout, KS, stride, pscale, pshift, Ho, Wo, slab, dw, db,
+         int(accumulate))
 
 
 def wgrad1x1_split_load_ok(dy, x):
     B, Cin, H, W = x.shape
     return (dy.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0
-            and _lib.lib().ubpl_wgrad1x1_split_load_workspace(B, Cin, dy.shape[1], H * W) > 0)
+            and _workspace("ubpl_wgrad1x1_split_load_workspace", B, Cin, dy.shape[1], H * W) > 0)
 
 
 def conv2d_wgrad1x1_split_load(dy, x, dw, db, pscale=None, pshift=None, accumulate=True, npieces=3):
@@ -489,23 +482,22 @@ def conv2d_wgrad1x1_split_load(dy, x, dw, db, pscale=None, pshift=None, accumula
     pshift) when pscale is given)."""
     B, Cin, H, W = x.shape
     Cout = dy.shape[1]
-    n = _lib.lib().ubpl_wgrad1x1_split_load_workspace(B, Cin, Cout, H * W)
-    slab = torch.empty(int(n), device=x.device, dtype=F32)
-    call("ubpl_wgrad1x1_split_load", _p(dy), _p(x), B, Cin, Cout, H * W, _p(pscale), _p(pshift), _p(slab), _p(dw),
-         _p(db), int(accumulate), int(npieces))
+    slab = _slab("ubpl_wgrad1x1_split_load_workspace", x.device, B, Cin, Cout, H * W)
+    call("ubpl_wgrad1x1_split_load", dy, x, B, Cin, Cout, H * W, pscale, pshift, slab, dw, db, int(accumulate),
+         int(npieces))
 
 
 def conv_weight_flip(w):
     """Data-gradient weights (stride 1), viewed as [Cin, KS*KS, Cout]."""
     Cout, Cin, KS, _ = w.shape
     wt = torch.empty((Cin, KS * KS, Cout), device=w.device, dtype=F32)
-    call("ubpl_conv_weight_flip", _p(w), Cout, Cin, KS, _p(wt))
+    call("ubpl_conv_weight_flip", w, Cout, Cin, KS, wt)
     return wt
 
 
 def conv_weights_relayout(src, dst, table, mode):
     """table: int64 [nseg,5] device tensor (src_off, dst_off, Cout, Cin, T)."""
-    call("ubpl_conv_weights_relayout", _p(src), _p(dst), _p(table), int(table.shape[0]), int(mode))
+    call("ubpl_conv_weights_relayout", src, dst, table, int(table.shape[0]), int(mode))
 
 
 # Conv arithmetic: "f32" = exact-f32 MFMA (v_mfma_f32_32x32x2_f32); "6xbf16" =
@@ -529,14 +521,12 @@ def backward_pieces(pieces):
 
 
 def conv_precision_name(name=None):
-    import os
     return name or os.environ.get("UBPL_CONV_PRECISION", DEFAULT_CONV_PRECISION)
 
 
 def conv_precision_pieces(name=None):
     """Pieces for a precision name (default: $UBPL_CONV_PRECISION or DEFAULT_CONV_PRECISION)."""
-    import os
-    name = name or os.environ.get("UBPL_CONV_PRECISION", DEFAULT_CONV_PRECISION)
+    name = conv_precision_name(name)
     if name not in CONV_PRECISIONS:
         raise ValueError("conv precision %r not in %s" % (name, sorted(CONV_PRECISIONS)))
     return CONV_PRECISIONS[name]
@@ -559,8 +549,7 @@ class SplitWeights:
 
 def conv_weights_split(src, dst, plane, table, mode, npieces):
     """Batched split re-layout (table as conv_weights_relayout, dst int16)."""
-    call("ubpl_conv_weights_split", _p(src), _p(dst), int(plane), _p(table), int(table.shape[0]), int(mode),
-         int(npieces))
+    call("ubpl_conv_weights_split", src, dst, int(plane), table, int(table.shape[0]), int(mode), int(npieces))
 
 
 def conv_weight_split(w, mode, npieces):
@@ -584,10 +573,9 @@ def conv2d_forward_split(x, ws, bias, pscale=None, pshift=None, res=None, out=No
         raise AssertionError("{} {}".format(Cin, wc))
     Ho, Wo = conv_out_hw(H, W, KS, 1)
     y = torch.empty((B, Cout, Ho, Wo), device=x.device, dtype=F32) if out is None else out
-    nws = _lib.lib().ubpl_conv2d_forward_split_workspace(B, Cin, Cout, KS, Ho, Wo, ws.npieces)
-    slab = torch.empty(int(nws), device=x.device, dtype=F32) if nws > 0 else None
-    call("ubpl_conv2d_forward_split", _p(x), B, Cin, H, W, ws.ptr(), int(ws.plane), _p(bias), Cout, KS, 1,
-         _p(pscale), _p(pshift), _p(res), _p(y), Ho, Wo, _p(slab), int(ws.npieces))
+    slab = _slab("ubpl_conv2d_forward_split_workspace", x.device, B, Cin, Cout, KS, Ho, Wo, ws.npieces, or_none=True)
+    call("ubpl_conv2d_forward_split", x, B, Cin, H, W, ws.ptr(), int(ws.plane), bias, Cout, KS, 1, pscale, pshift, res,
+         y, Ho, Wo, slab, int(ws.npieces))
     return y
 
 
@@ -619,8 +607,8 @@ def split_activation(x, npieces, pad, pscale=None, pshift=None, out=None, with3=
         if npieces != 2:
             raise ValueError("with3: the 2xfp16 split only")
         out3 = torch.empty(3 * plane, device=x.device, dtype=torch.int16)
-    call("ubpl_split_activation", _p(x), B, C, H, W, _p(pscale), _p(pshift), int(pad), int(npieces), _p(out),
-         int(plane), _p(out3), int(plane))
+    call("ubpl_split_activation", x, B, C, H, W, pscale, pshift, int(pad), int(npieces), out, int(plane), out3,
+         int(plane))
     xs = SplitAct(out, plane, B, C, H, W, pad, npieces)
     return (xs, SplitAct(out3, plane, B, C, H, W, pad, 3)) if with3 else xs
 
@@ -636,10 +624,9 @@ def conv2d_forward_psa(xs, ws, bias, res=None, out=None, stat_part=None, bwd=Non
         raise AssertionError("{} {} / pieces {} {}".format(xs.C, wc, xs.npieces, ws.npieces))
     B, H, W = xs.B, xs.H, xs.W
     y = torch.empty((B, Cout, H, W), device=xs.buf.device, dtype=F32) if out is None else out
-    nws = _lib.lib().ubpl_conv2d_forward_psa_workspace(B, xs.C, Cout, KS, H, W, ws.npieces)
-    slab = torch.empty(int(nws), device=xs.buf.device, dtype=F32) if nws > 0 else None
-    call("ubpl_conv2d_forward_psa", _p(xs.buf), int(xs.plane), B, xs.C, H, W, int(xs.pad), ws.ptr(), int(ws.plane),
-         _p(bias), Cout, KS, _p(res), _p(y), _p(slab), int(ws.npieces), _p(stat_part), *_bnb(bwd), _p(xs.scale))
+    slab = _slab("ubpl_conv2d_forward_psa_workspace", xs.buf.device, B, xs.C, Cout, KS, H, W, ws.npieces, or_none=True)
+    call("ubpl_conv2d_forward_psa", xs.buf, int(xs.plane), B, xs.C, H, W, int(xs.pad), ws.ptr(), int(ws.plane), bias,
+         Cout, KS, res, y, slab, int(ws.npieces), stat_part, *_bnb(bwd), xs.scale)
     return y
 
 
@@ -656,7 +643,7 @@ def stem_s2d_split(x, pad=2, npieces=3):
     Ho, Wo = H // 2, W // 2
     plane = B * (Ho + 2 * pad) * (Wo + 2 * pad) * 16
     buf = torch.empty(npieces * plane, device=x.device, dtype=torch.int16)
-    call("ubpl_stem_s2d_split", _p(x), B, C, H, W, int(pad), int(npieces), _p(buf), int(plane))
+    call("ubpl_stem_s2d_split", x, B, C, H, W, int(pad), int(npieces), buf, int(plane))
     return SplitAct(buf, plane, B, 16, Ho, Wo, pad, npieces)
 
 
@@ -671,7 +658,7 @@ def stem_weight_s2d_split(w, npieces=3, out=None):
         buf = out.buf
     else:
         buf = torch.empty(npieces * plane, device=w.device, dtype=torch.int16)
-    call("ubpl_stem_weight_s2d_split", _p(w.contiguous()), Cout, C, KS, int(npieces), _p(buf), int(plane))
+    call("ubpl_stem_weight_s2d_split", w.contiguous(), Cout, C, KS, int(npieces), buf, int(plane))
     return SplitWeights(buf, plane, 0, (Cout, 16, 16), npieces) if out is None else out
 
 
@@ -704,7 +691,7 @@ def _bnb(bwd):
     if bwd is None:
         return None, None, 0, None
     x, coef, relu, part = bwd
-    return _p(x), _p(coef), int(relu), _p(part)
+    return x, coef, int(relu), part
 
 
 def conv1x1_forward_split_load(x, ws, bias, pscale=None, pshift=None, res=None, out=None, stat_part=None,
@@ -720,8 +707,8 @@ def conv1x1_forward_split_load(x, ws, bias, pscale=None, pshift=None, res=None, 
         raise AssertionError("split-load 1x1: weights {} / pieces {} for {} input channels".format(
             ws.shape, ws.npieces, Cin))
     y = torch.empty((B, Cout, H, W), device=x.device, dtype=F32) if out is None else out
-    call("ubpl_conv1x1_forward_split_load", _p(x), B, Cin, H * W, ws.ptr(), int(ws.plane), _p(bias), Cout,
-         _p(pscale), _p(pshift), _p(res), _p(y), _p(stat_part), *_bnb(bwd), int(ws.npieces))
+    call("ubpl_conv1x1_forward_split_load", x, B, Cin, H * W, ws.ptr(), int(ws.plane), bias, Cout, pscale, pshift, res,
+         y, stat_part, *_bnb(bwd), int(ws.npieces))
     return y
 
 
@@ -732,10 +719,9 @@ def wgrad3_psa_ok(ys, xs):
 
 def conv2d_wgrad3_psa(ys, xs, dw, db, accumulate=True):
     """3x3 weight (+ bias) gradient from PSA operands: ys = split(dy), xs = split(conv input), pad 1."""
-    n = _lib.lib().ubpl_wgrad3_psa_workspace(xs.B, xs.C, ys.C, xs.H, xs.W)
-    slab = torch.empty(int(n), device=xs.buf.device, dtype=F32)
-    call("ubpl_wgrad3_psa", _p(ys.buf), int(ys.plane), _p(xs.buf), int(xs.plane), xs.B, xs.C, ys.C, xs.H, xs.W,
-         _p(slab), _p(dw), _p(db), int(accumulate), int(xs.npieces), _p(ys.scale))
+    slab = _slab("ubpl_wgrad3_psa_workspace", xs.buf.device, xs.B, xs.C, ys.C, xs.H, xs.W)
+    call("ubpl_wgrad3_psa", ys.buf, int(ys.plane), xs.buf, int(xs.plane), xs.B, xs.C, ys.C, xs.H, xs.W, slab, dw, db,
+         int(accumulate), int(xs.npieces), ys.scale)
 
 
 def wgrad_stem_psa_ok(ys, xs, w):
@@ -749,10 +735,9 @@ def conv2d_wgrad_stem_psa(ys, xs, dw, db, accumulate=True):
     """The 7x7/s2 stem's weight (+ bias) gradient from PSA operands: ys = split(dy) (pad 1),
     xs = the forward's space-to-depth phase image (stem_s2d_split, pad 2)."""
     Cout, C, KS = dw.shape[0], dw.shape[1], dw.shape[2]
-    n = _lib.lib().ubpl_wgrad_stem_psa_workspace(ys.B, Cout, ys.H, ys.W)
-    slab = torch.empty(int(n), device=ys.buf.device, dtype=F32)
-    call("ubpl_wgrad_stem_psa", _p(ys.buf), int(ys.plane), _p(xs.buf), int(xs.plane), ys.B, C, Cout, ys.H, ys.W, KS,
-         _p(slab), _p(dw), _p(db), int(accumulate), int(ys.npieces))
+    slab = _slab("ubpl_wgrad_stem_psa_workspace", ys.buf.device, ys.B, Cout, ys.H, ys.W)
+    call("ubpl_wgrad_stem_psa", ys.buf, int(ys.plane), xs.buf, int(xs.plane), ys.B, C, Cout, ys.H, ys.W, KS, slab, dw,
+         db, int(accumulate), int(ys.npieces))
 
 
 def conv2d_dgrad(dy, w, res=None, out=None, wt=None):
@@ -769,9 +754,9 @@ def maxpool2x2(x, out=None, stat_part=None):
     B, C, H, W = x.shape
     y = torch.empty((B, C, H // 2, W // 2), device=x.device, dtype=F32) if out is None else out
     if stat_part is not None:
-        call("ubpl_maxpool2x2_forward_stats", _p(x), B, C, H, W, _p(y), _p(stat_part))
+        call("ubpl_maxpool2x2_forward_stats", x, B, C, H, W, y, stat_part)
     else:
-        call("ubpl_maxpool2x2_forward", _p(x), B * C, H, W, _p(y))
+        call("ubpl_maxpool2x2_forward", x, B * C, H, W, y)
     return y
 
 
@@ -782,20 +767,20 @@ def stats_ok(H, W):
 
 def maxpool2x2_backward(x, dy, dx, accumulate):
     B, C, H, W = x.shape
-    call("ubpl_maxpool2x2_backward", _p(x), _p(dy), B * C, H, W, _p(dx), int(accumulate))
+    call("ubpl_maxpool2x2_backward", x, dy, B * C, H, W, dx, int(accumulate))
     return dx
 
 
 def avgpool2x2(x, out=None):
     B, C, H, W = x.shape
     y = torch.empty((B, C, H // 2, W // 2), device=x.device, dtype=F32) if out is None else out
-    call("ubpl_avgpool2x2_forward", _p(x), B * C, H, W, _p(y))
+    call("ubpl_avgpool2x2_forward", x, B * C, H, W, y)
     return y
 
 
 def avgpool2x2_backward(dy, dx, accumulate):
     B, C, H, W = dx.shape
-    call("ubpl_avgpool2x2_backward", _p(dy), B * C, H, W, _p(dx), int(accumulate))
+    call("ubpl_avgpool2x2_backward", dy, B * C, H, W, dx, int(accumulate))
     return dx
 
 
@@ -804,21 +789,21 @@ def upsample2x_add(up, low, out=None, stat_part=None):
     B, C, H, W = up.shape
     y = torch.empty_like(up) if out is None else out
     if stat_part is not None:
-        call("ubpl_upsample2x_add_forward_stats", _p(up), _p(low), B, C, H, W, _p(y), _p(stat_part))
+        call("ubpl_upsample2x_add_forward_stats", up, low, B, C, H, W, y, stat_part)
     else:
-        call("ubpl_upsample2x_add_forward", _p(up), _p(low), B * C, H, W, _p(y))
+        call("ubpl_upsample2x_add_forward", up, low, B * C, H, W, y)
     return y
 
 
 def upsample2x_add_backward(dout, dlow, accumulate):
     B, C, H, W = dout.shape
-    call("ubpl_upsample2x_add_backward", _p(dout), B * C, H, W, _p(dlow), int(accumulate))
+    call("ubpl_upsample2x_add_backward", dout, B * C, H, W, dlow, int(accumulate))
     return dlow
 
 
 def add(a, b, out=None):
     y = torch.empty_like(a) if out is None else out
-    call("ubpl_add", _p(a), _p(b), a.numel(), _p(y))
+    call("ubpl_add", a, b, a.numel(), y)
     return y
 
 
@@ -827,7 +812,7 @@ def image_mean_u8(imgs):
     """imgs uint8 [N,H,W,3] -> per-image mean / 255 (noisy_mean's mu), float32 [N]."""
     _chk(imgs, "imgs", torch.uint8)
     out = torch.empty(imgs.shape[0], device=imgs.device, dtype=F32)
-    call("ubpl_image_mean_u8", _p(imgs), imgs.shape[0], imgs[0].numel(), _p(out))
+    call("ubpl_image_mean_u8", imgs, imgs.shape[0], imgs[0].numel(), out)
     return out
 
 
@@ -840,8 +825,8 @@ def augment_warp(imgs, src_idx, mat, noise, img_mean, chan_mean, out):
     V, _, Ho, Wo = out.shape
     if mat.numel() != 6 * V or noise.numel() != 3 * V or src_idx.numel() != V:
         raise ValueError("augment_warp: per-view tables do not match %d views" % V)
-    call("ubpl_augment_warp", _p(imgs), imgs.shape[1], imgs.shape[2], _p(src_idx), _p(mat), _p(noise),
-         _p(img_mean), _p(chan_mean), V, Ho, Wo, _p(out))
+    call("ubpl_augment_warp", imgs, imgs.shape[1], imgs.shape[2], src_idx, mat, noise, img_mean, chan_mean, V, Ho, Wo,
+         out)
     return out
 
 
@@ -871,8 +856,8 @@ def augment_chain(imgs, geo, cs, noise, img_mean, chan_mean, Hm, Wm, out):
                          "(sigma %.3f px), which the device resize does not run; crops up to 1.3x are exact"
                          % (s, (s - 1) / 2))
     inter = torch.empty((V, 3, Hm, Wm), device=out.device, dtype=F32)
-    call("ubpl_augment_chain", _p(imgs), imgs.shape[1], imgs.shape[2], _p(geo), _p(cs), _p(noise), _p(img_mean),
-         _p(chan_mean), V, int(Hm), int(Wm), _p(inter), Ho, Wo, _p(out))
+    call("ubpl_augment_chain", imgs, imgs.shape[1], imgs.shape[2], geo, cs, noise, img_mean, chan_mean, V, int(Hm),
+         int(Wm), inter, Ho, Wo, out)
     return out
 
 
@@ -918,5 +903,5 @@ def occlude(out, bank, off, hw, pastes, view_first, chan_mean):
     if view_first.numel() != V + 1 or (pastes.numel() and pastes.shape[-1] != 9):
         raise ValueError("occlude: paste table does not match %d views" % V)
     _occlude_check(V, H, W, bank.numel(), off, hw, pastes, view_first)
-    call("ubpl_occlude", _p(out), V, H, W, _p(bank), _p(off), _p(hw), _p(pastes), _p(view_first), _p(chan_mean))
+    call("ubpl_occlude", out, V, H, W, bank, off, hw, pastes, view_first, chan_mean)
     return out
