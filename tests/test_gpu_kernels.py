@@ -309,6 +309,8 @@ CONV_CASES = [
     (8, 128, 32, 128, 3, 1, True, False),    # split-K in every pass
     (2, 64, 6, 32, 3, 1, True, False),       # Wo % 4 != 0: scalar wgrad path
     (3, 32, 5, 48, 1, 1, True, True),        # P % 4 != 0: scalar wgrad path
+    (1, 3, 12, 64, 7, 2, False, False),      # stem with Wo = 6: scalar wgrad path, generic forward loader
+    (2, 32, 6, 32, 3, 1, True, False),       # Wo = 6, Cin % 64 != 0: scalar wgrad path, n tiles across taps
 ]
 
 

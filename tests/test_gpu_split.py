@@ -1,6 +1,6 @@
 """Split MFMA convolutions (split_common.h and the split-path files beside it) vs float64 references.
 
-The exact-f32 MFMA path (conv.hip) is the yardstick: on the same inputs the
+The exact-f32 MFMA path (conv_f32_fwd.hip, conv_f32_wgrad.hip) is the yardstick: on the same inputs the
 3-piece bf16 path (npieces=3, "6xbf16", exact operands) and the 2-piece fp16
 path (npieces=2, "2xfp16": operands to 2^-22, 3 products) must land within
 F16_BAR / 2x the f32 path's own error against float64.  Weight re-layout,

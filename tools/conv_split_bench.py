@@ -1,4 +1,4 @@
-"""Forward-conv timing, exact-f32 MFMA (conv.hip) vs split-bf16 (conv_split_fwd.hip,
+"""Forward-conv timing, exact-f32 MFMA (conv_f32_fwd.hip) vs split-bf16 (conv_split_fwd.hip,
 2 and 3 pieces), for every conv shape of the 2-stack hourglass at batch B.
 
     python tools/conv_split_bench.py [B] [reps]

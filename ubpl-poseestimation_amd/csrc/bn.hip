@@ -5,7 +5,7 @@
 // Forward never materialises bn(x) for the residual branches: the statistics
 // kernels produce per-channel (scale, shift) = (g*invstd, b - mean*g*invstd)
 // — PyTorch's own transform form — and the consuming convolution applies
-// relu(x*scale + shift) while staging its operand (conv.hip prologue).
+// relu(x*scale + shift) while staging its operand (conv_f32_fwd.hip prologue).
 //
 // Statistics: each (channel, batch-slice) workgroup accumulates sum and sum of
 // squares of (x - x0) — x0 a sample of the channel, which removes the

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "ubpl_hip.h"
 
 #define UBPL_API extern "C" __attribute__((visibility("default")))
@@ -12,6 +14,15 @@
         hipError_t e__ = hipGetLastError();         \
         if (e__ != hipSuccess) return (int)e__;     \
     } while (0)
+
+typedef float floatx16 __attribute__((ext_vector_type(16)));
+typedef __attribute__((address_space(3))) void* lds_ptr_t;
+typedef __attribute__((address_space(1))) void* gbl_ptr_t;
+
+template <int N>
+__device__ __forceinline__ void vm_wait() {
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
 
 namespace ubpl {
 
@@ -306,5 +317,49 @@ __device__ __forceinline__ void tile_bn_bwd_partials(const ACC (&acc)[TM][TN], c
             }
     }
 }
+
+// ------------------------------------------------------------------ host side
+// compute units of the current device (256 when the query fails)
+inline int cu_count() {
+    static const int n = [] {
+        int dev = 0, v = 0;
+        const bool ok = hipGetDevice(&dev) == hipSuccess &&
+                        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0;
+        (void)hipGetLastError();
+        return ok ? v : 256;
+    }();
+    return n;
+}
+
+// A forward plan: tile height, split-K factor, K elements per split
+struct Plan {
+    int bm, splits, kchunk;
+};
+
+// ------------------------------------------------------------------ dispatch
+// Run-time values as compile-time ones: pick(f, among<1, 2, 3>{npieces}, among<128, 64>{bm})
+// calls the generic lambda f(auto NP, auto BM) with the std::integral_constant<int, V> of the V
+// each value equals, and returns its result; hipErrorInvalidValue when a value is none of its
+// list.  `if constexpr` inside f keeps out the combinations no kernel is built for.
+template <int... Vs>
+struct among {
+    int v;
+};
+template <class F>
+int pick(F&& f) {
+    return f();
+}
+template <class F, int... Vs, class... Rest>
+int pick(F&& f, among<Vs...> a, Rest... rest) {
+    int r = (int)hipErrorInvalidValue;
+    auto with = [&](auto c) { return pick([&](auto... cs) { return f(c, cs...); }, rest...); };
+    (void)((a.v == Vs && ((r = with(std::integral_constant<int, Vs>{})), true)) || ...);
+    return r;
+}
+
+// (conv_reduce.hip: y = sum of the split-K slab + bias (+ res), also after the register-staged kernel)
+__attribute__((visibility("hidden"))) void launch_split_reduce(const float* slab, int splits, int Cout, int P,
+                                                               int64_t N, const float* bias, const float* res,
+                                                               float* y, hipStream_t st);
 
 }  // namespace ubpl

@@ -159,7 +159,7 @@ __global__ void __launch_bounds__(NT, 2) conv_psa_kernel(const uint16_t* __restr
     const int nk16 = (k_end - k_begin) >> 4;               // 16-k steps
     const int nkt = (nk16 + KSUB - 1) / KSUB;              // stages
 
-    // accumulators start at bias (+ residual): see conv.hip conv_fwd_kernel
+    // accumulators start at bias (+ residual): see conv_f32_fwd.hip conv_fwd_kernel
     const int li = lane & 31, h = lane >> 5;
     int64_t obase[TN];
     bool nok[TN];
@@ -283,25 +283,6 @@ __global__ void __launch_bounds__(NT, 2) conv_psa_kernel(const uint16_t* __restr
     if (EPI && stat_part) ubpl::tile_bn_partials<TM, TN>(acc, nok, m0 + wm, Cout, n0 + wn, N, stat_part);
     if (EPI && bwd.part) ubpl::tile_bn_bwd_partials<TM, TN>(acc, nok, obase, m0 + wm, Cout, P, n0 + wn, N, bwd);
     store_tile<TM, TN>(acc, nok, obase, m0 + wm, Cout, P, y, m0 + BM <= Cout && n0 + BNT <= N, inv);
-}
-
-// y[b,m,p] = sum_z slab[z][m][b*P+p] + bias[m] (+ res)
-__global__ void __launch_bounds__(256) split_reduce_kernel(const float* __restrict__ slab, int splits, int Cout, int P,
-                                                          int64_t N, const float* __restrict__ bias, const float* res,
-                                                          float* y) {
-    const int64_t total = (int64_t)Cout * N;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int p = (int)(i % P);
-        const int64_t t = i / P;
-        const int m = (int)(t % Cout);
-        const int64_t b = t / Cout;
-        const int64_t n = b * P + p;
-        float s = 0.f;
-        for (int z = 0; z < splits; ++z) s += slab[((int64_t)z * Cout + m) * N + n];
-        if (bias) s += bias[m];
-        if (res) s += res[i];
-        y[i] = s;
-    }
 }
 
 using namespace ubpl;
@@ -457,14 +438,6 @@ int psa_launch(const PsaChoice& c, const PsaArgs& a) {
 }
 
 }  // namespace
-
-void ubpl::launch_split_reduce(const float* slab, int splits, int Cout, int P, int64_t N, const float* bias,
-                               const float* res, float* y, hipStream_t st) {
-    const int64_t total = (int64_t)Cout * N;
-    int gsz = (int)((total + 255) / 256);
-    if (gsz > 8192) gsz = 8192;
-    hipLaunchKernelGGL(split_reduce_kernel, dim3(gsz), dim3(256), 0, st, slab, splits, Cout, P, N, bias, res, y);
-}
 
 // Pre-split activations (PSA layout, see split_act_kernel): dst = npieces bf16
 // planes `plane` elements apart of [B][C/16][H+2pad][W+2pad][16];

@@ -9,7 +9,7 @@ namespace {
 // ------------------------------------------------------------------ forward
 // x NCHW f32; wp: NP planes (stride wplane elements) of the grouped tap-major
 // weights [Cout][Ktot] as bf16; Cin % 16 == 0.  Epilogue / split-K slab as
-// conv.hip's conv_fwd_kernel.
+// conv_f32_fwd.hip's conv_fwd_kernel.
 template <int BM, int KS, int ST, bool PRO, int NP>
 __global__ void __launch_bounds__(NT, 2) conv_fwd_split_kernel(
     const float* __restrict__ x, const uint16_t* __restrict__ wp, int64_t wplane, const float* __restrict__ bias,

@@ -12,7 +12,7 @@ namespace {
 // conv input = relu(bn(t1)), kept for the backward).  GEMM: M = co, N = (tap,
 // ci) tap-major (n-tile = one tap x 128 channels), K = pixels, K step = 16
 // consecutive pixels of one output row (W % 16 == 0), split over workgroups
-// into a slab [z][Cout][9*Cin + 1] reduced by conv.hip's wgrad_reduce_kernel
+// into a slab [z][Cout][9*Cin + 1] reduced by conv_reduce.hip's wgrad_reduce_kernel
 // (last column: the bias gradient, summed by the tap-0 workgroups).
 // The MFMA wants 8 consecutive pixels of one channel per lane, the PSA image
 // holds 16 channels per pixel: fragments come from LDS by
@@ -381,7 +381,7 @@ __global__ void __launch_bounds__(NT, 2) wgrad3_psa64_kernel(const uint16_t* __r
 // operands pixel-contiguous in NCHW (no transposes).  K step = 16 pixels of one
 // image (P % 16 == 0), split over workgroups into a slab [z][Cout][Cin + 1] (last
 // column: the bias gradient, from the Cin-tile-0 workgroups) reduced by
-// conv.hip's wgrad_reduce_kernel.  The f32 operands come global -> registers
+// conv_reduce.hip's wgrad_reduce_kernel.  The f32 operands come global -> registers
 // (two steps ahead), each element is split ONCE per workgroup by the thread
 // that loaded it (thread t: row t/2 of both operands, pixels 8(t&1)..+7), and
 // the pieces go to a double-buffered LDS image [operand][piece][128 rows][32 B]

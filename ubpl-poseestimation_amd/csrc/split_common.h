@@ -1,7 +1,7 @@
 // Shared by the split-precision convolution files (conv_split_fwd.hip, conv_psa.hip,
 // conv_psah.hip, conv1x1_sol.hip, conv_wgrad_split.hip, conv_stem_split.hip,
 // conv_weights_split.hip): the device helpers of every kernel family, and on the host side
-// the forward plan, the run-time knobs and the value selector of the dispatch.
+// the forward plan, the run-time knobs and the argument structs of the dispatch.
 //
 // Convolutions on the bf16 matrix cores with fp32 operands carried as sums of
 // bf16 pieces ("split-bf16"): v = v0 + v1 (+ v2), v0 = bf16(v), v1 = bf16(v - v0),
@@ -11,7 +11,7 @@
 // v_mfma_f32_32x32x16_bf16 into an f32 accumulator:
 //   NP = 2: 3 MFMAs per 32x32x16 step (16/3 = 5.3x the v_mfma_f32_32x32x2_f32 rate);
 //   NP = 3: 6 MFMAs (2.7x), rounding error at the level of an f32 fmaf chain.
-// Same GEMM views, K order and epilogues as conv.hip (the Conv wrapper,
+// Same GEMM views, K order and epilogues as conv_f32.h (the Conv wrapper,
 // models/base/layers.py:31-50): grouped tap-major k = (ci/16)*16T + tap*16 + ci%16.
 //
 // Operand images in LDS: [piece][row][4 x 16 B] with the row's 32 k of one
@@ -25,19 +25,15 @@
 #pragma once
 #include <atomic>
 #include <cstdlib>
-#include <type_traits>
 
 #include "common.h"
 using ubpl::xcd_remap;
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef short short8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef __attribute__((address_space(1))) void* gbl_ptr_t;
 
 // (the kernels and their helpers live in each file's own anonymous namespace)
 namespace {
@@ -183,11 +179,6 @@ __device__ __forceinline__ void store_tile(const floatx16 (&acc)[TM][TN], const 
     }
 }
 
-template <int N>
-__device__ __forceinline__ void vm_wait() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 }  // namespace
 
 // ------------------------------------------------------------------ host side
@@ -237,18 +228,6 @@ inline Knobs& knobs() {
     return k;
 }
 
-// compute units of the current device (256 when the query fails)
-inline int cu_count() {
-    static const int n = [] {
-        int dev = 0, v = 0;
-        const bool ok = hipGetDevice(&dev) == hipSuccess &&
-                        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0;
-        (void)hipGetLastError();
-        return ok ? v : 256;
-    }();
-    return n;
-}
-
 // Resident workgroups per CU of a family's 128- and 64-row forward kernels, [NP == 3]: each
 // family's file queries its own kernels (the initial values stay where a query fails).
 struct TileOcc {
@@ -269,10 +248,6 @@ inline TileOcc query_tile_occ(TileOcc r, const void* k128_2, const void* k128_3,
 }
 
 // ------------------------------------------------------------------ planning
-struct Plan {
-    int bm, splits, kchunk;
-};
-
 // Blocks spread evenly over the CUs; a CU with c blocks (r = min(c, occ)
 // resident) runs them in c * (steps + 2) K steps at a rate that needs ~2
 // resident blocks to hide latency.  Split-K adds the slab round trip + a launch.
@@ -331,26 +306,7 @@ inline float psa_osc(int np, int ktot, bool dev_act = false) {
 }
 
 // ------------------------------------------------------------------ dispatch
-// Run-time values as compile-time ones: pick(f, among<1, 2, 3>{npieces}, among<128, 64>{bm})
-// calls the generic lambda f(auto NP, auto BM) with the std::integral_constant<int, V> of the V
-// each value equals, and returns its result; hipErrorInvalidValue when a value is none of its
-// list.  `if constexpr` inside f keeps out the combinations no kernel is built for.
-template <int... Vs>
-struct among {
-    int v;
-};
-template <class F>
-int pick(F&& f) {
-    return f();
-}
-template <class F, int... Vs, class... Rest>
-int pick(F&& f, among<Vs...> a, Rest... rest) {
-    int r = (int)hipErrorInvalidValue;
-    auto with = [&](auto c) { return pick([&](auto... cs) { return f(c, cs...); }, rest...); };
-    (void)((a.v == Vs && ((r = with(std::integral_constant<int, Vs>{})), true)) || ...);
-    return r;
-}
-
+// (the value selector pick / among: common.h)
 // What every launch of ubpl_conv2d_forward_psa shares (conv_psa_kernel and conv_psah_kernel)
 struct PsaArgs {
     const uint16_t *xs, *wp;
@@ -379,9 +335,5 @@ struct PsaChoice {
 
 // (conv_psah.hip: its kernels build apart from conv_psa.hip's)
 __attribute__((visibility("hidden"))) int launch_psah(const PsaChoice& c, const PsaArgs& a);
-// (conv_psa.hip: y = sum of the split-K slab + bias (+ res), also after the register-staged kernel)
-__attribute__((visibility("hidden"))) void launch_split_reduce(const float* slab, int splits, int Cout, int P,
-                                                               int64_t N, const float* bias, const float* res,
-                                                               float* y, hipStream_t st);
 
 }  // namespace ubpl

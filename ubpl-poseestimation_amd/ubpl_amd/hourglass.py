@@ -14,7 +14,7 @@ models/__init__.py:4):
   running statistics live in `flat_stats` — so the EMA teacher update, the
   optimizer step and the DDP all-reduce are each a single kernel / collective
   over a contiguous buffer;
-* forward/backward are explicit executors over the HIP kernels (conv.hip with
+* forward/backward are explicit executors over the HIP kernels (the conv*.hip files with
   the pre-activation BN+ReLU fused into operand staging, bn.hip, pool.hip);
   autograd sees the whole network as one Function.
 """
@@ -325,7 +325,7 @@ class StackedHourglass(nn.Module):
 
     def set_conv_precision(self, name):
         """Conv arithmetic (kernels.CONV_PRECISIONS; None = $UBPL_CONV_PRECISION or the default):
-        'f32'    every conv on the exact-f32 MFMA (conv.hip);
+        'f32'    every conv on the exact-f32 MFMA (conv_f32_fwd.hip, conv1x1_dma.hip, conv_f32_wgrad.hip);
         '6xbf16' the 3x3 convs (forward and data gradient) on split-bf16 MFMA with
                  3 bf16 pieces per operand over pre-split activations (conv_psa.hip, conv_psah.hip
                  PSA path, error at the f32 path's level), the 1x1 convs whose
