@@ -412,6 +412,38 @@ int ubpl_maxpool2x2_forward_stats(const float* x, int B, int C, int H, int W, fl
 /*@ up:f32[(int64_t)B*C*H*W] low:f32[(int64_t)B*C*(H/2)*(W/2)] out:f32[(int64_t)B*C*H*W] part:f32[ubpl_bn_partial_floats(C,(int64_t)B*H*W)] */
 int ubpl_upsample2x_add_forward_stats(const float* up, const float* low, int B, int C, int H, int W, float* out,
                                       float* part, void* stream);
+/* The hourglass resampling passes folded into the BatchNorm kernel next to them
+ * (bn.hip).  Planes of H x W with H a power of two >= 2 and W/4 a power of two
+ * <= 32, C <= 512, f32 operands 16-byte aligned (half-resolution ones 8-byte);
+ * anything else returns hipErrorInvalidValue.  `part`: the statistics scratch of
+ * ubpl_bn_forward_stats.
+ * ubpl_bn_forward_stats_maxpool: ubpl_bn_forward_stats(x) for the BatchNorm of
+ * gamma .. shift (bit-identical; all eight null: x has no BatchNorm), y =
+ * ubpl_maxpool2x2_forward(x) (bit-identical) and the statistics of y for the
+ * BatchNorm of pgamma .. pshift (all eight null: not taken; f32 per thread about y[0,c,0], f64 across
+ * threads and slices, in a fixed order) in one launch. */
+/*@ x:f32[(int64_t)B*C*H*W] y:f32[(int64_t)B*C*(H/2)*(W/2)] gamma:f32[C] beta:f32[C] rmean:f32[C] rvar:f32[C] mean_out:f32[C] invstd_out:f32[C] scale:f32[C] shift:f32[C] pgamma:f32[C] pbeta:f32[C] prmean:f32[C] prvar:f32[C] pmean_out:f32[C] pinvstd_out:f32[C] pscale:f32[C] pshift:f32[C] part:f64[ubpl_bn_part_doubles(B,C)] */
+int ubpl_bn_forward_stats_maxpool(const float* x, int B, int C, int H, int W, float* y, const float* gamma,
+                                  const float* beta, float* rmean, float* rvar, float* mean_out, float* invstd_out,
+                                  float* scale, float* shift, const float* pgamma, const float* pbeta, float* prmean,
+                                  float* prvar, float* pmean_out, float* pinvstd_out, float* pscale, float* pshift,
+                                  float eps, float momentum, double* part, void* stream);
+/* out = ubpl_upsample2x_add_forward(up, low) (out may be up) and
+ * ubpl_bn_forward_stats(out) in one launch, both bit-identical. */
+/*@ up:f32[(int64_t)B*C*H*W] low:f32[(int64_t)B*C*(H/2)*(W/2)] out:f32[(int64_t)B*C*H*W] gamma:f32[C] beta:f32[C] rmean:f32[C] rvar:f32[C] part:f64[ubpl_bn_part_doubles(B,C)] mean_out:f32[C] invstd_out:f32[C] scale:f32[C] shift:f32[C] */
+int ubpl_upsample2x_add_forward_bnstats(const float* up, const float* low, int B, int C, int H, int W, float* out,
+                                        const float* gamma, const float* beta, float eps, float momentum,
+                                        float* rmean, float* rvar, double* part, float* mean_out, float* invstd_out,
+                                        float* scale, float* shift, void* stream);
+/* ubpl_bn_backward of x [B,C,H,W] with the gradient of y = maxpool2x2(x) folded
+ * into the apply: dx = ((dL/dx + add1) + maxpool2x2_backward(x, pool_dy)) + add2,
+ * bit-identical to ubpl_bn_backward(add1), ubpl_maxpool2x2_backward(accumulate)
+ * and ubpl_add in turn.  pool_dy [B,C,H/2,W/2] null: ubpl_bn_backward. */
+/*@ dz:f32[(int64_t)B*C*H*W] x:f32[(int64_t)B*C*H*W] gamma:f32[C] mean:f32[C] invstd:f32[C] scale:f32[C] shift:f32[C] scratch:f64[ubpl_bn_part_doubles(B,C)] part:f32[ubpl_bn_partial_floats(C,(int64_t)B*H*W)] coef:f32[3*C] dgamma:f32[C] dbeta:f32[C] add1:f32[(int64_t)B*C*H*W] pool_dy:f32[(int64_t)B*C*(H/2)*(W/2)] add2:f32[(int64_t)B*C*H*W] dx:f32[(int64_t)B*C*H*W] */
+int ubpl_bn_backward_pool(const float* dz, const float* x, int B, int C, int H, int W, const float* gamma,
+                          const float* mean, const float* invstd, const float* scale, const float* shift, int relu,
+                          double* scratch, const float* part, float* coef, float* dgamma, float* dbeta,
+                          const float* add1, const float* pool_dy, const float* add2, float* dx, void* stream);
 
 /* ---------------------------------------------------------------- f1 ----
  * Two-view training augmentation (DS_mds.__getitem__, datasets/dataset_mds.py:41-201:

@@ -137,6 +137,27 @@ struct StatsOut {
     float *rmean, *rvar, *mean_out, *invstd_out, *scale, *shift;
 };
 
+// Lane 0 of a channel's last block: the totals of (x - x0) -> the channel's statistics,
+// coefficients and running-statistics update (one expression for every statistics kernel:
+// the same rounding).
+__device__ __forceinline__ void finalize_stats(const StatsOut& o, int c, float x0, double t1, double t2, int64_t N) {
+    const double m1 = t1 / (double)N;
+    double var = t2 / (double)N - m1 * m1;
+    if (var < 0) var = 0;
+    const double mean = (double)x0 + m1;
+    const float invstd = (float)(1.0 / sqrt(var + (double)o.eps));
+    const float sc = invstd * o.gamma[c];
+    o.mean_out[c] = (float)mean;
+    o.invstd_out[c] = invstd;
+    o.scale[c] = sc;
+    o.shift[c] = o.beta[c] - (float)mean * sc;
+    if (o.rmean) {
+        const double unb = N > 1 ? var * (double)N / (double)(N - 1) : var;
+        o.rmean[c] = (float)((double)o.momentum * mean + (1.0 - (double)o.momentum) * (double)o.rmean[c]);
+        o.rvar[c] = (float)((double)o.momentum * unb + (1.0 - (double)o.momentum) * (double)o.rvar[c]);
+    }
+}
+
 // One (channel c, batch slice) per block over the flattened (b, pixel) range:
 // sum and sum of squares of (x - x0), x0 = x[0, c, 0]; f32 per thread, f64
 // across the block and the slices.  The last block of channel c finalizes it.
@@ -217,22 +238,7 @@ __global__ void __launch_bounds__(256) stats_kernel(const float* __restrict__ x,
     const double d2 = ubpl::block_sum((double)s2, red);
     double t1, t2;
     if (!combine_slices(part + (int64_t)c * chan_stride(gridDim.y), sp, gridDim.y, cnt + c, d1, d2, t1, t2)) return;
-    const int64_t N = (int64_t)B * HW;
-    const double m1 = t1 / (double)N;
-    double var = t2 / (double)N - m1 * m1;
-    if (var < 0) var = 0;
-    const double mean = (double)x0 + m1;
-    const float invstd = (float)(1.0 / sqrt(var + (double)o.eps));
-    const float sc = invstd * o.gamma[c];
-    o.mean_out[c] = (float)mean;
-    o.invstd_out[c] = invstd;
-    o.scale[c] = sc;
-    o.shift[c] = o.beta[c] - (float)mean * sc;
-    if (o.rmean) {
-        const double unb = N > 1 ? var * (double)N / (double)(N - 1) : var;
-        o.rmean[c] = (float)((double)o.momentum * mean + (1.0 - (double)o.momentum) * (double)o.rmean[c]);
-        o.rvar[c] = (float)((double)o.momentum * unb + (1.0 - (double)o.momentum) * (double)o.rvar[c]);
-    }
+    finalize_stats(o, c, x0, t1, t2, (int64_t)B * HW);
 }
 
 // Eval-mode scale / shift of one channel (one expression for both kernels below: the same rounding)
@@ -1047,6 +1053,387 @@ UBPL_API int ubpl_bn_backward(const float* dz, const float* x, int B, int C, int
     else
         hipLaunchKernelGGL(bwd_apply_kernel, dim3(grid_ew(total)), dim3(256), 0, st, dz, x, C, HW, total, scale,
                            shift, mean, relu, ca, cb, cc, add1, add2, dx);
+    UBPL_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// The hourglass resampling passes (pool.hip) folded into the BatchNorm kernel
+// next to them in the chain, which already holds the tensor in registers:
+//   stats_maxpool_kernel   statistics of x + MaxPool2d(2,2) of x + statistics of the pooled tensor
+//   upadd_stats_kernel     out = up + upsample2x(low) + statistics of out
+//   bwd_apply_pool_*       the BN backward apply + the max-pool gradient + the second addend
+// Geometry (pool_geom): planes of H x W floats, H a power of two >= 2, W/4 (float4s per
+// row) a power of two <= 32.  Then a plane is hw4 = H*W/4 float4s, a power of two, and
+//  * float4 `off` of the tensor is plane off >> lhw4, row (off & (hw4-1)) >> lw4, column
+//    off & (W/4-1): shifts, no division;
+//  * the float4 one row below / above (the other half of its two 2x2 windows) is float4
+//    off ^ (W/4), held by lane ^ (W/4) of the same wave in the same iteration: on
+//    visit_chan4's whole-row path and in bwd_apply_pool_plane_kernel a thread's float4s sit
+//    at threadIdx.x + 256 k of the plane, on the flattened paths at a multiple of 256 from
+//    threadIdx.x with 256 a multiple of hw4 (or hw4 of 256) — and a lane is active exactly
+//    when its partner is (the ranges end on plane boundaries);
+//  * the half-resolution tensor's plane is hw4 floats = hw4/2 float2s, W/4 float2s a row.
+namespace {
+
+struct PoolGeom {
+    int lw4, lhw4;   // log2(W/4), log2(H*W/4)
+};
+
+bool pool_geom(int H, int W, PoolGeom& g) {
+    if (H < 2 || W < 4 || (H & (H - 1)) || (W & 3)) return false;
+    const int w4 = W >> 2;
+    if ((w4 & (w4 - 1)) || w4 > 32) return false;
+    g.lw4 = __builtin_ctz(w4);
+    g.lhw4 = g.lw4 + __builtin_ctz(H);
+    return g.lhw4 < 28;
+}
+
+// Maximum of a 2x2 window given in row-major order and its position: the first maximum,
+// a NaN wins (maxpool_fwd_kernel / maxpool_bwd_kernel's rule).
+__device__ __forceinline__ float max4(float a, float b, float c, float d, int& am) {
+    float m = a;
+    am = 0;
+    if (b > m || isnan(b)) { m = b; am = 1; }
+    if (c > m || isnan(c)) { m = c; am = 2; }
+    if (d > m || isnan(d)) { m = d; am = 3; }
+    return m;
+}
+
+__device__ __forceinline__ float4 shfl_xor4(float4 v, int m) {
+    return make_float4(__shfl_xor(v.x, m, 64), __shfl_xor(v.y, m, 64), __shfl_xor(v.z, m, 64),
+                       __shfl_xor(v.w, m, 64));
+}
+
+// float2 index, in the half-resolution tensor, of the two windows float4 `off` belongs to
+__device__ __forceinline__ int64_t half_index(int64_t off, PoolGeom g) {
+    const int o4 = (int)(off & ((1 << g.lhw4) - 1));
+    return ((off >> g.lhw4) << (g.lhw4 - 1)) + (((o4 >> g.lw4) >> 1) << g.lw4) + (o4 & ((1 << g.lw4) - 1));
+}
+
+// combine_slices with two pairs of sums per slice (combine_slices4's layout: 4 doubles per
+// slice, channel stride chan_stride(2 * nsp)), all four summed in the same fixed order.
+// True in lane 0 of the channel's last block, with the totals.
+__device__ __forceinline__ bool combine_slices2x2(double* pc, int sp, int nsp, unsigned* cnt, double d1, double d2,
+                                                  double d3, double d4, double& t1, double& t2, double& t3,
+                                                  double& t4) {
+    if (threadIdx.x >= 64) return false;
+    const int lane = threadIdx.x;
+    int last = 0;
+    if (lane == 0) {
+        publish2(pc + sp * 4, d1, d2);
+        publish2(pc + sp * 4 + 2, d3, d4);
+        last = last_arriver(cnt, nsp) ? 1 : 0;
+    }
+    if (!__shfl(last, 0, 64)) return false;
+    t1 = t2 = t3 = t4 = 0.0;
+    for (int q = lane; q < nsp; q += 64) {
+        t1 += consume(pc + q * 4);
+        t2 += consume(pc + q * 4 + 1);
+        t3 += consume(pc + q * 4 + 2);
+        t4 += consume(pc + q * 4 + 3);
+    }
+    t1 = ubpl::wave_sum(t1);
+    t2 = ubpl::wave_sum(t2);
+    t3 = ubpl::wave_sum(t3);
+    t4 = ubpl::wave_sum(t4);
+    return lane == 0;
+}
+
+// stats_kernel<true> over x (same elements per thread, same order: the statistics of x are
+// bit-identical; `o` unused when o.scale is null) which also writes y = maxpool2x2(x) and
+// accumulates the statistics of y for the BatchNorm `op` that consumes it: the thread
+// holding the top row of two windows takes the bottom row from its partner lane, writes the
+// two maxima (one float2) and adds them to its sums of (y - y0) and (y - y0)^2, y0 = y[0, c, 0],
+// left window then right, in its visiting order; f64 across the block and the slices like
+// x's sums.  The channel's last block finalizes both BatchNorms from the one ticket.
+template <int U = 4>
+__global__ void __launch_bounds__(256) stats_maxpool_kernel(const float* __restrict__ x, int B, int C, int HW,
+                                                           int bper, PoolGeom g, float* __restrict__ y,
+                                                           double* __restrict__ part, unsigned* __restrict__ cnt,
+                                                           StatsOut o, StatsOut op) {
+    __shared__ double red[16];
+    const int c = blockIdx.x, sp = blockIdx.y;
+    const int b0 = sp * bper, b1 = min(B, b0 + bper);
+    const float* xc = x + (int64_t)c * HW;
+    const float x0 = xc[0];
+    const int W = 4 << g.lw4, w4 = 1 << g.lw4;
+    int am;
+    const float y0 = max4(xc[0], xc[1], xc[W], xc[W + 1], am);
+    float s1 = 0.f, s2 = 0.f, s3 = 0.f, s4 = 0.f;
+    const float4* x4 = reinterpret_cast<const float4*>(x);
+    float2* y2 = reinterpret_cast<float2*>(y);
+    visit_chan4<U>(b0, b1, C, c, HW >> 2, [&](int, int64_t off) {
+        const float4 v = x4[off];
+        const float a = v.x - x0, q = v.y - x0, r = v.z - x0, d = v.w - x0;
+        s1 += (a + q) + (r + d);
+        s2 = fmaf(a, a, fmaf(q, q, fmaf(r, r, fmaf(d, d, s2))));
+        const float4 w = shfl_xor4(v, w4);
+        if (!((off >> g.lw4) & 1)) {   // an even row: the top halves
+            int t;
+            const float m0 = max4(v.x, v.y, w.x, w.y, t), m1 = max4(v.z, v.w, w.z, w.w, t);
+            y2[half_index(off, g)] = make_float2(m0, m1);
+            const float e = m0 - y0, f = m1 - y0;
+            s3 += e + f;
+            s4 = fmaf(e, e, fmaf(f, f, s4));
+        }
+    });
+    const double d1 = ubpl::block_sum((double)s1, red);
+    const double d2 = ubpl::block_sum((double)s2, red);
+    const double d3 = ubpl::block_sum((double)s3, red);
+    const double d4 = ubpl::block_sum((double)s4, red);
+    double t1, t2, t3, t4;
+    if (!combine_slices2x2(part + (int64_t)c * chan_stride(2 * gridDim.y), sp, gridDim.y, cnt + c, d1, d2, d3, d4,
+                           t1, t2, t3, t4))
+        return;
+    if (o.scale) finalize_stats(o, c, x0, t1, t2, (int64_t)B * HW);
+    if (op.scale) finalize_stats(op, c, y0, t3, t4, (int64_t)B * (HW >> 2));
+}
+
+// upadd_fwd_vec_kernel's sum, out = up + upsample2x(low), on stats_kernel<true>'s grid and
+// in its visiting order, followed by the statistics of out for the BatchNorm that consumes
+// it: bit-identical to the two launches.  out may be up (each float4 read, then written, by
+// one thread).  x0 = out[0, c, 0] is computed by every block from up and low; so that no
+// block reads up[0, c, 0] after an in-place store, the float4 holding it is stored by the
+// channel's last block, after the ticket (every block's x0 load has returned by then: its
+// published sums depend on it).
+template <int U = 4>
+__global__ void __launch_bounds__(256) upadd_stats_kernel(const float* up, const float* __restrict__ low, int B,
+                                                         int C, int HW, int bper, PoolGeom g, float* out,
+                                                         double* __restrict__ part, unsigned* __restrict__ cnt,
+                                                         StatsOut o) {
+    __shared__ double red[16];
+    const int c = blockIdx.x, sp = blockIdx.y;
+    const int b0 = sp * bper, b1 = min(B, b0 + bper);
+    const int hw4 = HW >> 2;
+    const int64_t first = (int64_t)c * hw4;   // the float4 of out[0, c, 0]
+    const float x0 = up[(int64_t)c * HW] + low[(int64_t)c * hw4];
+    float s1 = 0.f, s2 = 0.f;
+    const float4* u4 = reinterpret_cast<const float4*>(up);
+    const float2* l2 = reinterpret_cast<const float2*>(low);
+    float4* o4 = reinterpret_cast<float4*>(out);
+    visit_chan4<U>(b0, b1, C, c, hw4, [&](int, int64_t off) {
+        const float4 u = u4[off];
+        const float2 l = l2[half_index(off, g)];
+        const float4 v = make_float4(u.x + l.x, u.y + l.x, u.z + l.y, u.w + l.y);
+        if (off != first) o4[off] = v;
+        const float a = v.x - x0, q = v.y - x0, r = v.z - x0, d = v.w - x0;
+        s1 += (a + q) + (r + d);
+        s2 = fmaf(a, a, fmaf(q, q, fmaf(r, r, fmaf(d, d, s2))));
+    });
+    const double d1 = ubpl::block_sum((double)s1, red);
+    const double d2 = ubpl::block_sum((double)s2, red);
+    double t1, t2;
+    if (!combine_slices(part + (int64_t)c * chan_stride(gridDim.y), sp, gridDim.y, cnt + c, d1, d2, t1, t2)) return;
+    const float4 u = u4[first];
+    const float2 l = l2[half_index(first, g)];
+    o4[first] = make_float4(u.x + l.x, u.y + l.x, u.z + l.y, u.w + l.y);
+    finalize_stats(o, c, x0, t1, t2, (int64_t)B * HW);
+}
+
+// The max-pool gradient's share of one float4 of dx: pd holds the two windows' gradients;
+// the float4's elements that are their windows' argmax (max4's rule over the window in
+// row-major order, the other row from the partner lane) take them, every other element
+// adds 0.f, as maxpool_bwd_kernel's accumulate does (-0 + 0 = +0: bit-identical).
+__device__ __forceinline__ void add_pool_grad(float4& v, float4 xv, int64_t off, PoolGeom g, float2 pd) {
+    const float4 w = shfl_xor4(xv, 1 << g.lw4);
+    const bool bot = (off >> g.lw4) & 1;
+    const float4 t = bot ? w : xv, b = bot ? xv : w;
+    int a0, a1;
+    max4(t.x, t.y, b.x, b.y, a0);
+    max4(t.z, t.w, b.z, b.w, a1);
+    const int q = bot ? 2 : 0;
+    v.x += a0 == q ? pd.x : 0.f;
+    v.y += a0 == q + 1 ? pd.x : 0.f;
+    v.z += a1 == q ? pd.y : 0.f;
+    v.w += a1 == q + 1 ? pd.y : 0.f;
+}
+
+// bwd_apply_vec_kernel + the max-pool gradient: dx = ((bn + add1) + pool) + add2, the order
+// of ubpl_bn_backward(add1), ubpl_maxpool2x2_backward(accumulate) and ubpl_add.
+__global__ void __launch_bounds__(256) bwd_apply_pool_vec_kernel(const float* dz, const float* __restrict__ x, int C,
+                                                                int HW4, int64_t total4,
+                                                                const float* __restrict__ scale,
+                                                                const float* __restrict__ shift,
+                                                                const float* __restrict__ mean, int relu,
+                                                                const float* __restrict__ ca,
+                                                                const float* __restrict__ cb,
+                                                                const float* __restrict__ cc, const float* add1,
+                                                                const float* __restrict__ pool_dy, PoolGeom pg,
+                                                                const float* add2, float* dx) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += stride) {
+        const int c = (int)((i >> pg.lhw4) % C);
+        const float sc = scale[c], sh = shift[c], mu = mean[c], a = ca[c], b = cb[c], cx = cc[c];
+        const float4 xv = reinterpret_cast<const float4*>(x)[i];
+        const float4 g = reinterpret_cast<const float4*>(dz)[i];
+        const float2 pd = reinterpret_cast<const float2*>(pool_dy)[half_index(i, pg)];
+        float4 v;
+        v.x = bwd_one(g.x, xv.x, sc, sh, mu, a, b, cx, relu);
+        v.y = bwd_one(g.y, xv.y, sc, sh, mu, a, b, cx, relu);
+        v.z = bwd_one(g.z, xv.z, sc, sh, mu, a, b, cx, relu);
+        v.w = bwd_one(g.w, xv.w, sc, sh, mu, a, b, cx, relu);
+        if (add1) {
+            const float4 q = reinterpret_cast<const float4*>(add1)[i];
+            v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w;
+        }
+        add_pool_grad(v, xv, i, pg, pd);
+        if (add2) {
+            const float4 q = reinterpret_cast<const float4*>(add2)[i];
+            v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w;
+        }
+        reinterpret_cast<float4*>(dx)[i] = v;
+    }
+}
+
+// bwd_apply_plane_kernel + the max-pool gradient (HW4 % 256 == 0; every operand's U loads first).
+template <int U>
+__global__ void __launch_bounds__(256) bwd_apply_pool_plane_kernel(const float* dz, const float* __restrict__ x, int C,
+                                                                  int HW4, const float* __restrict__ scale,
+                                                                  const float* __restrict__ shift,
+                                                                  const float* __restrict__ mean, int relu,
+                                                                  const float* __restrict__ ca,
+                                                                  const float* __restrict__ cb,
+                                                                  const float* __restrict__ cc, const float* add1,
+                                                                  const float* __restrict__ pool_dy, PoolGeom pg,
+                                                                  const float* add2, float* dx) {
+    const int pl = blockIdx.y;
+    const int c = pl % C;
+    const float sc = scale[c], sh = shift[c], mu = mean[c], a = ca[c], b = cb[c], cx = cc[c];
+    const int64_t base = (int64_t)pl * HW4 + blockIdx.x * (256 * U) + threadIdx.x;
+    const float4* x4 = reinterpret_cast<const float4*>(x) + base;
+    const float4* d4 = reinterpret_cast<const float4*>(dz) + base;
+    float4 xv[U], g[U], q1[U], q2[U];
+    float2 pd[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        xv[u] = x4[u * 256];
+        g[u] = d4[u * 256];
+        pd[u] = reinterpret_cast<const float2*>(pool_dy)[half_index(base + u * 256, pg)];
+        if (add1) q1[u] = reinterpret_cast<const float4*>(add1)[base + u * 256];
+        if (add2) q2[u] = reinterpret_cast<const float4*>(add2)[base + u * 256];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        float4 v;
+        v.x = bwd_one(g[u].x, xv[u].x, sc, sh, mu, a, b, cx, relu);
+        v.y = bwd_one(g[u].y, xv[u].y, sc, sh, mu, a, b, cx, relu);
+        v.z = bwd_one(g[u].z, xv[u].z, sc, sh, mu, a, b, cx, relu);
+        v.w = bwd_one(g[u].w, xv[u].w, sc, sh, mu, a, b, cx, relu);
+        if (add1) { v.x += q1[u].x; v.y += q1[u].y; v.z += q1[u].z; v.w += q1[u].w; }
+        add_pool_grad(v, xv[u], base + u * 256, pg, pd[u]);
+        if (add2) { v.x += q2[u].x; v.y += q2[u].y; v.z += q2[u].z; v.w += q2[u].w; }
+        reinterpret_cast<float4*>(dx)[base + u * 256] = v;
+    }
+}
+
+// the (channel, batch slice) grid of a statistics launch
+void stats_grid(int B, int C, int HW, int& bper, int& gs) {
+    const int splits = splits_for(B, C, HW);
+    bper = (B + splits - 1) / splits;
+    gs = (B + bper - 1) / bper;
+}
+
+}  // namespace
+
+// ubpl_bn_forward_stats(x) for the BatchNorm of (gamma, beta, ...) — all eight null: no
+// BatchNorm on x — with y = maxpool2x2(x) [B,C,H/2,W/2] and the statistics of y for the
+// BatchNorm of (pgamma, pbeta, ...) — all eight null: not wanted — from the same launch.  H a power of two, W/4 a power
+// of two <= 32, C <= 512, x 16-byte and y 8-byte aligned; anything else is refused.
+UBPL_API int ubpl_bn_forward_stats_maxpool(const float* x, int B, int C, int H, int W, float* y, const float* gamma,
+                                           const float* beta, float* rmean, float* rvar, float* mean_out,
+                                           float* invstd_out, float* scale, float* shift, const float* pgamma,
+                                           const float* pbeta, float* prmean, float* prvar, float* pmean_out,
+                                           float* pinvstd_out, float* pscale, float* pshift, float eps,
+                                           float momentum, double* part, void* stream) {
+    PoolGeom g;
+    if (B < 1 || C < 1 || C > MAXBN || !pool_geom(H, W, g) || (((uintptr_t)x) & 15) || (((uintptr_t)y) & 7) ||
+        part == nullptr || y == nullptr)
+        return (int)hipErrorInvalidValue;
+    const bool own = scale != nullptr;
+    if (own ? !(gamma && beta && mean_out && invstd_out && shift) : (gamma || beta || rmean || rvar || mean_out ||
+                                                                    invstd_out || shift) != 0)
+        return (int)hipErrorInvalidValue;
+    if (pscale ? !(pgamma && pbeta && pmean_out && pinvstd_out && pshift) : (pgamma || pbeta || prmean || prvar ||
+                                                                             pmean_out || pinvstd_out || pshift) != 0)
+        return (int)hipErrorInvalidValue;
+    int bper, gs;
+    stats_grid(B, C, H * W, bper, gs);
+    unsigned* cnt = reinterpret_cast<unsigned*>(part);
+    part += CNT_DOUBLES;
+    const StatsOut o{gamma, beta, eps, momentum, rmean, rvar, mean_out, invstd_out, scale, shift};
+    const StatsOut op{pgamma, pbeta, eps, momentum, prmean, prvar, pmean_out, pinvstd_out, pscale, pshift};
+    hipLaunchKernelGGL(stats_maxpool_kernel<4>, dim3(C, gs), dim3(256), 0, (hipStream_t)stream, x, B, C, H * W, bper,
+                       g, y, part, cnt, o, op);
+    UBPL_LAUNCH_CHECK();
+    return 0;
+}
+
+// out = up + upsample2x(low) (ubpl_upsample2x_add_forward; out may be up) and
+// ubpl_bn_forward_stats(out) in one launch, both bit-identical.  Geometry as above; up /
+// out 16-byte, low 8-byte aligned.
+UBPL_API int ubpl_upsample2x_add_forward_bnstats(const float* up, const float* low, int B, int C, int H, int W,
+                                                 float* out, const float* gamma, const float* beta, float eps,
+                                                 float momentum, float* rmean, float* rvar, double* part,
+                                                 float* mean_out, float* invstd_out, float* scale, float* shift,
+                                                 void* stream) {
+    PoolGeom g;
+    if (B < 1 || C < 1 || C > MAXBN || !pool_geom(H, W, g) || ((((uintptr_t)up) | ((uintptr_t)out)) & 15) ||
+        (((uintptr_t)low) & 7) || part == nullptr || out == nullptr)
+        return (int)hipErrorInvalidValue;
+    if (!(gamma && beta && mean_out && invstd_out && scale && shift)) return (int)hipErrorInvalidValue;
+    int bper, gs;
+    stats_grid(B, C, H * W, bper, gs);
+    unsigned* cnt = reinterpret_cast<unsigned*>(part);
+    part += CNT_DOUBLES;
+    const StatsOut o{gamma, beta, eps, momentum, rmean, rvar, mean_out, invstd_out, scale, shift};
+    hipLaunchKernelGGL(upadd_stats_kernel<4>, dim3(C, gs), dim3(256), 0, (hipStream_t)stream, up, low, B, C, H * W,
+                       bper, g, out, part, cnt, o);
+    UBPL_LAUNCH_CHECK();
+    return 0;
+}
+
+// ubpl_bn_backward of x [B,C,H,W] with the gradient of y = maxpool2x2(x) folded into the
+// apply: dx = ((dL/dx + add1) + maxpool2x2_backward(x, pool_dy)) + add2, bit-identical to
+// ubpl_bn_backward(add1), ubpl_maxpool2x2_backward(accumulate) and ubpl_add in turn.
+// pool_dy [B,C,H/2,W/2] null: ubpl_bn_backward.  With it: geometry as above, every f32
+// operand 16-byte and pool_dy 8-byte aligned.
+UBPL_API int ubpl_bn_backward_pool(const float* dz, const float* x, int B, int C, int H, int W, const float* gamma,
+                                   const float* mean, const float* invstd, const float* scale, const float* shift,
+                                   int relu, double* scratch, const float* part, float* coef, float* dgamma,
+                                   float* dbeta, const float* add1, const float* pool_dy, const float* add2,
+                                   float* dx, void* stream) {
+    const int HW = H * W;
+    if (pool_dy == nullptr)
+        return ubpl_bn_backward(dz, x, B, C, HW, gamma, mean, invstd, scale, shift, relu, scratch, part, coef, dgamma,
+                                dbeta, add1, add2, dx, stream);
+    PoolGeom g;
+    const uintptr_t al = (uintptr_t)dz | (uintptr_t)x | (uintptr_t)dx | (uintptr_t)add1 | (uintptr_t)add2;
+    if (B < 1 || C < 1 || !pool_geom(H, W, g) || (al & 15) || (((uintptr_t)pool_dy) & 7))
+        return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream;
+    const int e = bwd_stats(dz, x, B, C, HW, gamma, mean, invstd, scale, shift, relu, scratch, part, coef, dgamma,
+                            dbeta, st);
+    if (e) return e;
+    const float *ca = coef, *cb = coef + C, *cc = coef + 2 * C;
+    const int hw4 = HW / 4;
+    if (hw4 % 256 == 0 && (int64_t)B * C < 65536) {
+        const int u = hw4 % 1024 == 0 ? 4 : (hw4 % 512 == 0 ? 2 : 1);
+        const dim3 grid((unsigned)(hw4 / (256 * u)), (unsigned)(B * C));
+        if (u == 4)
+            hipLaunchKernelGGL(bwd_apply_pool_plane_kernel<4>, grid, dim3(256), 0, st, dz, x, C, hw4, scale, shift,
+                               mean, relu, ca, cb, cc, add1, pool_dy, g, add2, dx);
+        else if (u == 2)
+            hipLaunchKernelGGL(bwd_apply_pool_plane_kernel<2>, grid, dim3(256), 0, st, dz, x, C, hw4, scale, shift,
+                               mean, relu, ca, cb, cc, add1, pool_dy, g, add2, dx);
+        else
+            hipLaunchKernelGGL(bwd_apply_pool_plane_kernel<1>, grid, dim3(256), 0, st, dz, x, C, hw4, scale, shift,
+                               mean, relu, ca, cb, cc, add1, pool_dy, g, add2, dx);
+    } else {
+        const int64_t total4 = (int64_t)B * C * hw4;
+        hipLaunchKernelGGL(bwd_apply_pool_vec_kernel, dim3(grid_ew(total4)), dim3(256), 0, st, dz, x, C, hw4, total4,
+                           scale, shift, mean, relu, ca, cb, cc, add1, pool_dy, g, add2, dx);
+    }
     UBPL_LAUNCH_CHECK();
     return 0;
 }

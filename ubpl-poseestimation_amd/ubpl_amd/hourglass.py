@@ -63,6 +63,16 @@ _RELAYOUT_ONCE = os.environ.get("UBPL_RELAYOUT_ONCE", "0") == "1"
 # diagnostic (tools/fwd_race.py locate): keep low3 (the add's second operand) as a saved activation
 # ("1": the tensor itself, kept alive; "clone": a copy made right after it is produced)
 _SAVE_LOW3 = os.environ.get("UBPL_SAVE_LOW3", "")
+# the hourglass max-pool / upsample-add passes folded into the BatchNorm kernels next to them
+# (bn.hip stats_maxpool_kernel, upadd_stats_kernel, bwd_apply_pool_*).  UBPL_POOL_FUSE=0: the
+# separate launches; 1 (default): every fusion whose results are bit-identical to those launches
+# (the pooled tensor's own statistics stay a stats_kernel launch); 2: the pooled tensor's
+# statistics from the pooling kernel too — one launch less per level, but a new summation order,
+# so the step no longer computes bit for bit what the separate launches do.  Training forwards on
+# planes Kn.pool_fuse_ok takes only, and off under the diagnostics that reroute the same
+# statistics or keep the add's operands
+_POOL_FUSE = 0 if (_PRODUCER_STATS or _FWD_EPI or _UPADD_OOP or _SAVE_LOW3) else \
+    {"0": 0, "2": 2}.get(os.environ.get("UBPL_POOL_FUSE", "1"), 1)
 
 
 # ---------------------------------------------------------------------------
@@ -572,15 +582,19 @@ class StackedHourglass(nn.Module):
         x = ex.stem(imgs)
         x = ex.residual("pre.1", x)
         x1 = x
-        part = ex.stat_buffer((x1.shape[0], x1.shape[1], x1.shape[2] // 2, x1.shape[3] // 2))
-        x = Kn.maxpool2x2(x1, stat_part=part)
-        ex.give_part(x, part)
+        if ex.fuse_ok(x1) and ex.fuse == 2:
+            x = ex.bn_maxpool(None, x1, "pre.3.bn1")       # (no BatchNorm takes x1 itself)
+            ex.give_coef(x, "pre.3.bn1")
+        else:
+            part = ex.stat_buffer((x1.shape[0], x1.shape[1], x1.shape[2] // 2, x1.shape[3] // 2))
+            x = Kn.maxpool2x2(x1, stat_part=part)
+            ex.give_part(x, part)
         ex.save("pre.2", x1)
         x = ex.residual("pre.3", x)
         x = ex.residual("pre.4", x)
         preds, feats = [], []
         for i in range(self.nStack):
-            hg = ex.hourglass("hgs.%d.0" % i, 4, x)
+            hg = ex.hourglass("hgs.%d.0" % i, 4, x, "features.%d.0.bn1" % i)
             f0 = ex.residual("features.%d.0" % i, hg)
             f = ex.conv_bn_relu("features.%d.1" % i, f0)
             if self.mode != "default" and not frozen:
@@ -671,6 +685,8 @@ class _Exec:
         self.saved = {}
         self.saved_split = {}
         self._rp = None     # (tensor, BN partials of it) from its producer, for the next residual's bn1
+        self._rc = None     # (tensor, BN name): its producer filled that BN's coefficients (the fused pool kernels)
+        self.fuse = _POOL_FUSE if train else 0      # (0 / 1 / 2: see _POOL_FUSE)
         self.cidx, C = model._coef_index()
         # per BN: scale|shift|mean|invstd
         self.coef = self.ws.coef if self.ws.frozen else torch.empty(4 * C, device=dev)
@@ -688,6 +704,30 @@ class _Exec:
     def take_part(self, x):
         rp, self._rp = self._rp, None
         return rp[1] if rp is not None and rp[0] is x else None
+
+    def give_coef(self, y, bn):
+        """y's producer computed BatchNorm bn's statistics of it (coefficients and running
+        statistics written): the residual that takes y next launches nothing for its bn1."""
+        self._rc = (y, bn)
+
+    def take_coef(self, x, bn):
+        rc, self._rc = self._rc, None
+        return rc is not None and rc[0] is x and rc[1] == bn
+
+    def fuse_ok(self, x):
+        """x [B,C,H,W] takes the fused pool / upsample-add + BatchNorm kernels (training forward)."""
+        return self.fuse > 0 and Kn.pool_fuse_ok(x.shape[2], x.shape[3], x.shape[1], x)
+
+    def _bn_args(self, name):
+        sc, sh, mu, istd = self.bnc(name)
+        rm, rv = self.m.stats(name)
+        return self.ws.P(name + ".weight"), self.ws.P(name + ".bias"), rm, rv, mu, istd, sc, sh
+
+    def bn_maxpool(self, bn, x, pbn):
+        """bn's statistics of x (None: no BatchNorm on x), maxpool2x2(x) and pbn's statistics
+        of the pooled tensor in one launch (the caller hands them over: give_coef)."""
+        return Kn.bn_forward_stats_maxpool(x, None if bn is None else self._bn_args(bn),
+                                           None if pbn is None else self._bn_args(pbn), BN_EPS, BN_MOMENTUM, self.part)
 
     def stat_buffer(self, x_shape):
         """Partials buffer for an elementwise producer's output (None: not on this path)."""
@@ -793,7 +833,8 @@ class _Exec:
         """models/base/layers.py:69-84 (pre-activation bottleneck)."""
         cin = x.shape[1]
         cout = self.m._offs[p + ".conv3.conv.weight"][2][0]
-        c1 = self.bn(p + ".bn1", x, self.take_part(x))
+        part = self.take_part(x)
+        c1 = self.bnc(p + ".bn1")[:2] if self.take_coef(x, p + ".bn1") else self.bn(p + ".bn1", x, part)
         t1, part = self.conv(p + ".conv1.conv", x, pro=c1, stats=True)
         c2 = self.bn(p + ".bn2", t1, part)
         t2, part = self.conv(p + ".conv2.conv", t1, pro=c2, stats=True)
@@ -807,18 +848,35 @@ class _Exec:
         self.give_part(out, part)
         return out
 
-    def hourglass(self, p, n, x):
-        """models/base/layers.py:104-111."""
-        up1 = self.residual(p + ".up1", x)
-        part = self.stat_buffer((x.shape[0], x.shape[1], x.shape[2] // 2, x.shape[3] // 2))
-        pl = Kn.maxpool2x2(x, stat_part=part)
-        self.give_part(pl, part)
+    def hourglass(self, p, n, x, consumer=None):
+        """models/base/layers.py:104-111.  consumer: the BatchNorm that takes the result
+        (the bn1 of the residual after it), for the fused upsample-add."""
+        if self.fuse_ok(x):
+            # up1.bn1's statistics launch also pools x
+            # (fuse == 2 only: and takes low1.bn1's statistics of the pooled tensor)
+            pl = self.bn_maxpool(p + ".up1.bn1", x, p + ".low1.bn1" if self.fuse == 2 else None)
+            self.give_coef(x, p + ".up1.bn1")
+            up1 = self.residual(p + ".up1", x)
+            if self.fuse == 2:
+                self.give_coef(pl, p + ".low1.bn1")
+        else:
+            up1 = self.residual(p + ".up1", x)
+            part = self.stat_buffer((x.shape[0], x.shape[1], x.shape[2] // 2, x.shape[3] // 2))
+            pl = Kn.maxpool2x2(x, stat_part=part)
+            self.give_part(pl, part)
         low1 = self.residual(p + ".low1", pl)
-        low2 = self.hourglass(p + ".low2", n - 1, low1) if n > 1 else self.residual(p + ".low2", low1)
+        low2 = self.hourglass(p + ".low2", n - 1, low1, p + ".low3.bn1") if n > 1 else \
+            self.residual(p + ".low2", low1)
         low3 = self.residual(p + ".low3", low2)
         if _SAVE_LOW3 in ("1", "clone"):                 # diagnostic: the residual's output before the add
             self.save(p + ".low3_out", low3.clone() if _SAVE_LOW3 == "clone" else low3)
         self.save(p, x)
+        if consumer is not None and self.fuse_ok(up1) and low3.data_ptr() % 8 == 0:
+            # the add in place, with the consumer's statistics of the sum
+            out = Kn.upsample2x_add_bnstats(up1, low3, self._bn_args(consumer), BN_EPS, BN_MOMENTUM, self.part,
+                                            out=up1)
+            self.give_coef(out, consumer)
+            return out
         part = self.stat_buffer(up1.shape)
         if _UPADD_OOP:                                   # diagnostic: up1 kept, the sum in a new tensor
             self.save(p + ".up1_out", up1)
@@ -841,9 +899,14 @@ class _Exec:
         s, n, shp = self.m._offs[name]
         return self.gbuf[s:s + n].view(shp)
 
-    def bn_bwd(self, name, dz, x, relu, add1=None, add2=None, out=None, part=None):
-        """part: the backward partials dz's producer wrote (None: a statistics pass)."""
+    def bn_bwd(self, name, dz, x, relu, add1=None, add2=None, out=None, part=None, pool_dy=None):
+        """part: the backward partials dz's producer wrote (None: a statistics pass);
+        pool_dy: the gradient of maxpool2x2(x), added between add1 and add2."""
         sc, sh, mu, istd = self.bnc(name)
+        if pool_dy is not None:
+            return Kn.bn_backward_pool(dz, x, self.m.P(name + ".weight"), mu, istd, sc, sh, relu, self.bpart,
+                                       self._coef(), self.G(name + ".weight"), self.G(name + ".bias"), add1=add1,
+                                       pool_dy=pool_dy, add2=add2, out=out, part=part)
         return Kn.bn_backward(dz, x, self.m.P(name + ".weight"), mu, istd, sc, sh, relu, self.bpart, self._coef(),
                               self.G(name + ".weight"), self.G(name + ".bias"), add1=add1, add2=add2, out=out,
                               part=part)
@@ -896,7 +959,9 @@ class _Exec:
             return Kn.conv1x1_forward_kmajor(dy, w, None, res=res, out=out)     # [Cout][Cin] = k-major
         return Kn.conv2d_dgrad(dy, None, res=res, out=out, wt=self.m.W(1, name + ".weight"))
 
-    def residual_bwd(self, p, dout):
+    def residual_bwd(self, p, dout, pool_dy=None, add2=None):
+        """pool_dy / add2: folded into the final bn1 apply (the input was also max-pooled;
+        a second gradient of the input), see bn_bwd."""
         x, t1, t2 = self.saved.get(p)
         cin = x.shape[1]
         cout = dout.shape[1]
@@ -939,10 +1004,11 @@ class _Exec:
         if cin != cout:
             self.wgrad(p + ".skip_layer.conv", dout, x, 1)
             ds = self.dgrad(p + ".skip_layer.conv", dout)
-            return self.bn_bwd(p + ".bn1", d, x, relu=1, add1=ds, part=part)
-        return self.bn_bwd(p + ".bn1", d, x, relu=1, add1=dout, part=part)
+            return self.bn_bwd(p + ".bn1", d, x, relu=1, add1=ds, part=part, pool_dy=pool_dy, add2=add2)
+        return self.bn_bwd(p + ".bn1", d, x, relu=1, add1=dout, part=part, pool_dy=pool_dy, add2=add2)
 
-    def hourglass_bwd(self, p, n, dout):
+    def hourglass_bwd(self, p, n, dout, add2=None):
+        """add2: a second gradient of the hourglass input (the next stack's), added last."""
         x = self.saved.get(p)
         B, C, H, W = dout.shape
         dlow3 = torch.empty((B, C, H // 2, W // 2), device=self.dev)
@@ -950,8 +1016,13 @@ class _Exec:
         dlow2 = self.residual_bwd(p + ".low3", dlow3)
         dlow1 = self.hourglass_bwd(p + ".low2", n - 1, dlow2) if n > 1 else self.residual_bwd(p + ".low2", dlow2)
         dpl = self.residual_bwd(p + ".low1", dlow1)
+        if _POOL_FUSE and Kn.pool_fuse_ok(x.shape[2], x.shape[3], x.shape[1], x, dout, dpl, add2):
+            # the pool's gradient and add2 inside up1.bn1's backward apply
+            return self.residual_bwd(p + ".up1", dout, pool_dy=dpl, add2=add2)
         dx = self.residual_bwd(p + ".up1", dout)
         Kn.maxpool2x2_backward(x, dpl, dx, accumulate=True)
+        if add2 is not None:
+            dx = Kn.add(dx, add2, out=dx)
         return dx
 
     def backward(self, dpreds, dfeats):
@@ -989,10 +1060,7 @@ class _Exec:
             self.wgrad("features.%d.1.conv" % i, d, f0, 1)
             d = self.dgrad("features.%d.1.conv" % i, d)
             d = self.residual_bwd("features.%d.0" % i, d)
-            dx = self.hourglass_bwd("hgs.%d.0" % i, 4, d)
-            if dxn is not None:
-                dx = Kn.add(dx, dxn, out=dx)
-            dxn = dx
+            dxn = self.hourglass_bwd("hgs.%d.0" % i, 4, d, add2=dxn)
         d = self.residual_bwd("pre.4", dxn)
         d = self.residual_bwd("pre.3", d)
         x1 = self.saved.get("pre.2")

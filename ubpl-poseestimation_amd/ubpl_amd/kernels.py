@@ -807,6 +807,97 @@ def add(a, b, out=None):
     return y
 
 
+# ------------------------------------------------------------------ pool / upsample folded into BatchNorm
+def pool_fuse_ok(H, W, C=1, *tensors):
+    """Planes the fused resampling + BatchNorm kernels take (bn.hip pool_geom): H and W
+    even, W/4 a power of two <= 32 (the 2x2 windows' other row sits in lane ^ (W/4) of the
+    same wave), H a power of two (planes divide, or are a power-of-two multiple of, a
+    256-thread block's float4s), C <= 512 (the statistics scratch's tickets) and every
+    tensor given 16-byte aligned."""
+    if H < 2 or W < 4 or H & (H - 1) or W & 3:
+        return False
+    w4 = W >> 2
+    if w4 & (w4 - 1) or w4 > 32 or not 1 <= C <= 512:
+        return False
+    return all(t is None or t.data_ptr() % 16 == 0 for t in tensors)
+
+
+def _same_shape(name, t, shape):
+    if t is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError("ubpl_amd: %s has shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
+
+
+def _fuse_geometry(name, x):
+    if x.dim() != 4:
+        raise ValueError("ubpl_amd: %s takes a [B,C,H,W] tensor, got shape %s" % (name, tuple(x.shape)))
+    B, C, H, W = x.shape
+    if B < 1 or not pool_fuse_ok(H, W, C):
+        raise ValueError("ubpl_amd: %s does not take planes of %dx%d with %d channels (pool_fuse_ok)" % (name, H, W, C))
+    return B, C, H, W
+
+
+def bn_forward_stats_maxpool(x, xbn, pbn, eps, momentum, part, out=None):
+    """One launch: bn_forward_stats(x) for the BatchNorm xbn (None: x has none),
+    y = maxpool2x2(x), and the statistics of y for the BatchNorm pbn (None: not taken; a new
+    summation order, unlike everything else here).  xbn / pbn:
+    (gamma, beta, rmean, rvar, mean, invstd, scale, shift), rmean / rvar nullable."""
+    B, C, H, W = _fuse_geometry("bn_forward_stats_maxpool", x)
+    for nm, bn in (("xbn", xbn), ("pbn", pbn)):
+        if bn is None:
+            continue
+        if len(bn) != 8:
+            raise ValueError("ubpl_amd: %s is (gamma, beta, rmean, rvar, mean, invstd, scale, shift)" % nm)
+        for i, t in enumerate(bn):
+            _same_shape("%s[%d]" % (nm, i), t, (C,))
+    _same_shape("out", out, (B, C, H // 2, W // 2))
+    _chk(x, "x")
+    y = torch.empty((B, C, H // 2, W // 2), device=x.device, dtype=F32) if out is None else out
+    call("ubpl_bn_forward_stats_maxpool", x, B, C, H, W, y, *(xbn if xbn is not None else (None,) * 8),
+         *(pbn if pbn is not None else (None,) * 8),
+         float(eps), float(momentum), part)
+    return y
+
+
+def upsample2x_add_bnstats(up, low, bn, eps, momentum, part, out=None):
+    """One launch: out = upsample2x_add(up, low) (out=up: in place) and bn_forward_stats(out)
+    for the BatchNorm bn = (gamma, beta, rmean, rvar, mean, invstd, scale, shift)."""
+    B, C, H, W = _fuse_geometry("upsample2x_add_bnstats", up)
+    _same_shape("low", low, (B, C, H // 2, W // 2))
+    _same_shape("out", out, up.shape)
+    if bn is None or len(bn) != 8:
+        raise ValueError("ubpl_amd: bn is (gamma, beta, rmean, rvar, mean, invstd, scale, shift)")
+    for i, t in enumerate(bn):
+        _same_shape("bn[%d]" % i, t, (C,))
+    _chk(up, "up")
+    _chk(low, "low")
+    y = torch.empty_like(up) if out is None else out
+    gamma, beta, rmean, rvar, mean, invstd, scale, shift = bn
+    call("ubpl_upsample2x_add_forward_bnstats", up, low, B, C, H, W, y, gamma, beta, float(eps), float(momentum),
+         rmean, rvar, part, mean, invstd, scale, shift)
+    return y
+
+
+def bn_backward_pool(dz, x, gamma, mean, invstd, scale, shift, relu, scratch, coef, dgamma, dbeta, add1=None,
+                     pool_dy=None, add2=None, out=None, part=None):
+    """bn_backward with the gradient of maxpool2x2(x) folded into the apply:
+    dx = ((dL/dx + add1) + maxpool2x2_backward(x, pool_dy)) + add2, bit-identical to
+    bn_backward(add1), maxpool2x2_backward(accumulate=True) and add in turn."""
+    if pool_dy is None:
+        return bn_backward(dz, x, gamma, mean, invstd, scale, shift, relu, scratch, coef, dgamma, dbeta, add1=add1,
+                           add2=add2, out=out, part=part)
+    B, C, H, W = _fuse_geometry("bn_backward_pool", x)
+    for nm, t in (("dz", dz), ("add1", add1), ("add2", add2), ("out", out)):
+        _same_shape(nm, t, x.shape)
+    _same_shape("pool_dy", pool_dy, (B, C, H // 2, W // 2))
+    _chk(x, "x")
+    _chk(dz, "dz")
+    _chk(pool_dy, "pool_dy")
+    dx = dz if out is None else out
+    call("ubpl_bn_backward_pool", dz, x, B, C, H, W, gamma, mean, invstd, scale, shift, int(relu), scratch, part, coef,
+         dgamma, dbeta, add1, pool_dy, add2, dx)
+    return dx
+
+
 # ------------------------------------------------------------------ f1
 def image_mean_u8(imgs):
     """imgs uint8 [N,H,W,3] -> per-image mean / 255 (noisy_mean's mu), float32 [N]."""
