@@ -160,7 +160,6 @@ int ubpl_scale_(float* x, int64_t n, float s, void* stream);
  * use (arrival counters for C <= 512 channels at its head, which each call
  * leaves at zero, then the partial sums; one call at a time per scratch).  rmean/rvar updated with momentum
  * (nullable).  scale = gamma*invstd, shift = beta - mean*scale. */
-int ubpl_bn_splits(int B, int C);
 int64_t ubpl_bn_part_doubles(int B, int C);
 /*@ x:f32[(int64_t)B*C*HW] gamma:f32[C] beta:f32[C] rmean:f32[C] rvar:f32[C] part:f64[ubpl_bn_part_doubles(B,C)] mean_out:f32[C] invstd_out:f32[C] scale:f32[C] shift:f32[C] */
 int ubpl_bn_forward_stats(const float* x, int B, int C, int HW, const float* gamma, const float* beta, float eps,
@@ -413,7 +412,7 @@ int ubpl_maxpool2x2_forward_stats(const float* x, int B, int C, int H, int W, fl
 int ubpl_upsample2x_add_forward_stats(const float* up, const float* low, int B, int C, int H, int W, float* out,
                                       float* part, void* stream);
 /* The hourglass resampling passes folded into the BatchNorm kernel next to them
- * (bn.hip).  Planes of H x W with H a power of two >= 2 and W/4 a power of two
+ * (bn_fwd.hip, bn_bwd.hip).  Planes of H x W with H a power of two >= 2 and W/4 a power of two
  * <= 32, C <= 512, f32 operands 16-byte aligned (half-resolution ones 8-byte);
  * anything else returns hipErrorInvalidValue.  `part`: the statistics scratch of
  * ubpl_bn_forward_stats.

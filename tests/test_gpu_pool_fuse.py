@@ -1,5 +1,5 @@
 """The hourglass max-pool / upsample-add passes folded into the BatchNorm kernels
-next to them (bn.hip: ubpl_bn_forward_stats_maxpool, ubpl_upsample2x_add_forward_bnstats,
+next to them (bn_fwd.hip: ubpl_bn_forward_stats_maxpool, ubpl_upsample2x_add_forward_bnstats; bn_bwd.hip:
 ubpl_bn_backward_pool) against the launch sequences they replace.
 
 Shapes (B, C, H=W): the smallest that reach every path — the flattened small-plane path

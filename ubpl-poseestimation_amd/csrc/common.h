@@ -274,7 +274,7 @@ __device__ __forceinline__ void tile_bn_partials(const ACC (&acc)[TM][TN], const
 // BatchNorm BACKWARD partials of a data-gradient tile (the conv output is dz
 // of the BN whose input is x): per channel m and 64-pixel slice q,
 // (S1, S2) = (sum g, sum g*(x - mean)), g = dz under the recomputed ReLU mask
-// — bn.hip bn_bwd_partials_kernel's layout and formula, from the accumulators
+// — bn_bwd.hip bn_bwd_partials_kernel's layout and formula, from the accumulators
 // (no dz re-read; x is read at the tile's own addresses).
 struct BnBwdEpi {
     const float* x;      // BN input [B][M][P] (nullptr: off)

@@ -71,7 +71,7 @@ __global__ void __launch_bounds__(NT, 2) conv_psa_kernel(const uint16_t* __restr
                                                         const float* __restrict__ ascp) {
     // osc: the accumulators' scale (2xfp16: weight scale x activation scale, the latter
     // read from *ascp when the image's scale lives on the device — a data gradient's,
-    // bn.hip fp16_scale_for; 1 on the other paths)
+    // bn_bwd.hip fp16_scale_for; 1 on the other paths)
     if (ascp != nullptr) osc *= *ascp;
     constexpr int PADK = KS / 2;   // odd KS: centred; even KS (the stem, 4x4): taps -KS/2 .. KS/2 - 1
     constexpr int T = KS * KS;

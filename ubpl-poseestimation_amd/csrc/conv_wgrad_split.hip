@@ -26,7 +26,7 @@ __global__ void __launch_bounds__(NT, 2) wgrad3_psa_kernel(const uint16_t* __res
                                                           const uint16_t* __restrict__ xs, int64_t xplane, int B,
                                                           int Cin, int Cout, int H, int W, int steps_per_split,
                                                           float* __restrict__ slab, const float* __restrict__ dscale) {
-    // NP = 2 (2xfp16): dys are the fp16 pieces of dy * (*dscale) (bn.hip fp16_scale_for), xs of
+    // NP = 2 (2xfp16): dys are the fp16 pieces of dy * (*dscale) (bn_bwd.hip fp16_scale_for), xs of
     // x * FP16_ACT_SCALE (the forward's image): the slab gets the products unscaled exactly.
     // CB = channel block of both tile sides (128, or 64 for the 64-channel convs:
     // wave tile 32 x 32, waves 0-1 move the operands)

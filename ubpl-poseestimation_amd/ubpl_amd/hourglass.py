@@ -15,7 +15,7 @@ models/__init__.py:4):
   optimizer step and the DDP all-reduce are each a single kernel / collective
   over a contiguous buffer;
 * forward/backward are explicit executors over the HIP kernels (the conv*.hip files with
-  the pre-activation BN+ReLU fused into operand staging, bn.hip, pool.hip);
+  the pre-activation BN+ReLU fused into operand staging, bn_fwd.hip / bn_bwd.hip, pool.hip);
   autograd sees the whole network as one Function.
 """
 import math
@@ -51,7 +51,7 @@ _STEM_WGRAD = os.environ.get("UBPL_STEM_WGRAD", "1") != "0"
 # statistics pass (stats_kernel) on the training step.
 _FWD_EPI = os.environ.get("UBPL_FWD_EPI", "0") == "1"
 # 2xfp16: the 3x3 data / weight gradients on 2xfp16 too (dy scaled by the BN backward's bound of
-# it, bn.hip bwd_stats_kernel BOUND); UBPL_FP16_BWD3=0: on 6xbf16 (with the forward's 6xbf16 image
+# it, bn_bwd.hip bwd_stats_kernel BOUND); UBPL_FP16_BWD3=0: on 6xbf16 (with the forward's 6xbf16 image
 # kept for the weight gradient)
 _FP16_BWD3 = os.environ.get("UBPL_FP16_BWD3", "1") != "0"
 # diagnostic (tools/graph_fwd_probe.py locate): the hourglass upsample-add out of place, its
@@ -64,7 +64,7 @@ _RELAYOUT_ONCE = os.environ.get("UBPL_RELAYOUT_ONCE", "0") == "1"
 # ("1": the tensor itself, kept alive; "clone": a copy made right after it is produced)
 _SAVE_LOW3 = os.environ.get("UBPL_SAVE_LOW3", "")
 # the hourglass max-pool / upsample-add passes folded into the BatchNorm kernels next to them
-# (bn.hip stats_maxpool_kernel, upadd_stats_kernel, bwd_apply_pool_*).  UBPL_POOL_FUSE=0: the
+# (bn_fwd.hip stats_maxpool_kernel, upadd_stats_kernel; bn_bwd.hip bwd_apply_*_kernel<true>).  UBPL_POOL_FUSE=0: the
 # separate launches; 1 (default): every fusion whose results are bit-identical to those launches
 # (the pooled tensor's own statistics stay a stats_kernel launch); 2: the pooled tensor's
 # statistics from the pooling kernel too — one launch less per level, but a new summation order,

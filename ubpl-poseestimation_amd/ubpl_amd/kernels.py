@@ -302,10 +302,6 @@ def scale_(x, s):
 
 
 # ------------------------------------------------------------------ BN
-def bn_splits(B, C):
-    return _lib.lib().ubpl_bn_splits(B, C)
-
-
 def bn_part(B, C, device):
     """Zeroed BN scratch (partial sums + self-resetting arrival counters)."""
     return torch.zeros(int(_lib.lib().ubpl_bn_part_doubles(B, C)), dtype=torch.float64, device=device)
@@ -809,7 +805,7 @@ def add(a, b, out=None):
 
 # ------------------------------------------------------------------ pool / upsample folded into BatchNorm
 def pool_fuse_ok(H, W, C=1, *tensors):
-    """Planes the fused resampling + BatchNorm kernels take (bn.hip pool_geom): H and W
+    """Planes the fused resampling + BatchNorm kernels take (bn.h pool_geom): H and W
     even, W/4 a power of two <= 32 (the 2x2 windows' other row sits in lane ^ (W/4) of the
     same wave), H a power of two (planes divide, or are a power-of-two multiple of, a
     256-thread block's float4s), C <= 512 (the statistics scratch's tickets) and every
