@@ -154,6 +154,38 @@ int ubpl_adamw_ema_step_dev(float* p, const float* g, float* m, float* v, int64_
 /*@ x:f32[n] */
 int ubpl_scale_(float* x, int64_t n, float s, void* stream);
 
+/* Guarded optimizer step: global gradient-norm clip (torch.nn.utils.clip_grad_norm_)
+ * and a non-finite guard, all through device memory so a captured step replays it.
+ * ubpl_grad_guard reads the gradient prefix g[0, n) once (n a multiple of 4, g 16-B
+ * aligned; part: ubpl_grad_guard_scratch(n) doubles of caller-owned scratch) and writes
+ * guard[4] = {c, norm, skip, 0}: the squares are summed in f64 in a fixed order (equal
+ * input, equal bits); skip = 1.0 iff the sum is not finite (some element is inf or NaN);
+ * c = min(1, max_norm / (norm + 1e-6)) in f64 rounded once, 1 when max_norm <= 0 or the
+ * step is skipped; norm is the f32 rounding of the f64 L2 norm.  n == 0: {1, 0, 0, 0}. */
+int64_t ubpl_grad_guard_scratch(int64_t n);
+/*@ g:f32[n] part:f64[ubpl_grad_guard_scratch(n)] guard:f32[4] */
+int ubpl_grad_guard(const float* g, int64_t n, double max_norm, double* part, float* guard, void* stream);
+/* ubpl_adamw_step_dev / ubpl_adamw_ema_step_dev under such a guard: the gradient is
+ * taken as g * guard[0] (one f32 product in registers; g is not written), so guard[0] == 1
+ * is bit-identical to the unguarded entry and any other value to ubpl_scale_(g, c)
+ * followed by it.  When guard[2] != 0 the step count, p, m and v are untouched and
+ * skipped[0] (total) and skipped[1] (consecutive) are incremented; a step that runs
+ * zeroes skipped[1].  The EMA half runs either way (toward the unchanged student on a
+ * skipped step: ubpl_ema_update alone). */
+/*@ p:f32[n] g:f32[n] m:f32[n] v:f32[n] step:i64[1] coef:f32[4] guard:f32[4] skipped:i64[2] */
+int ubpl_adamw_step_guarded_dev(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1,
+                                double beta2, double eps, double weight_decay, int64_t* step, float* coef,
+                                const float* guard, int64_t* skipped, void* stream);
+/*@ p:f32[n] g:f32[nlive] m:f32[nlive] v:f32[nlive] step:i64[1] coef:f32[4] ema:f32[n] guard:f32[4] skipped:i64[2] */
+int ubpl_adamw_ema_step_guarded_dev(float* p, const float* g, float* m, float* v, int64_t nlive, double lr,
+                                    double beta1, double beta2, double eps, double weight_decay, int64_t* step,
+                                    float* coef, float* ema, int64_t n, double alpha, const float* guard,
+                                    int64_t* skipped, void* stream);
+/* dst[0, n) = saved[0, n) when guard[2] != 0, else nothing (BatchNorm running
+ * statistics after a skipped step). */
+/*@ dst:f32[n] saved:f32[n] guard:f32[4] */
+int ubpl_restore_if(float* dst, const float* saved, int64_t n, const float* guard, void* stream);
+
 /* ---------------------------------------------------------------- H2-H4 --
  * BatchNorm2d (models/base/layers.py:41,57-61), train-mode statistics.
  * part: scratch of ubpl_bn_part_doubles(B,C) doubles, ZEROED before its first

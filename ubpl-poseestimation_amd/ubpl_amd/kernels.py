@@ -301,6 +301,44 @@ def scale_(x, s):
     call("ubpl_scale_", x, x.numel(), float(s))
 
 
+def grad_guard_scratch(n, device):
+    """The f64 scratch grad_guard_ needs for a gradient of n floats."""
+    return torch.zeros(int(_lib.lib().ubpl_grad_guard_scratch(int(n))), dtype=torch.float64, device=device)
+
+
+def grad_guard_(g, max_norm, part, guard):
+    """guard[4] = {clip coefficient, L2 norm, skip, 0} of the flat gradient g (numel a
+    multiple of 4, 16-B aligned): clip_grad_norm_'s coefficient for max_norm (<= 0: no
+    clipping), skip = 1.0 iff some element is inf or NaN.  part: grad_guard_scratch."""
+    _chk(g, "g")
+    call("ubpl_grad_guard", g, g.numel(), float(max_norm), part, guard)
+
+
+def adamw_step_guarded_dev_(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step_t, coef, guard, skipped):
+    """adamw_step_dev_ on g * guard[0]; a no-op but for skipped[2] (int64: total,
+    consecutive) when guard[2] is set."""
+    call("ubpl_adamw_step_guarded_dev", p, g, m, v, p.numel(), float(lr), float(beta1), float(beta2), float(eps),
+         float(weight_decay), step_t, coef, guard, skipped)
+
+
+def adamw_ema_step_guarded_dev_(p, g, m, v, nlive, lr, beta1, beta2, eps, weight_decay, step_t, coef, ema, alpha,
+                                guard, skipped):
+    """adamw_ema_step_dev_ under a guard: on a skipped step only the EMA half runs."""
+    if ema.numel() != p.numel() or nlive > p.numel():
+        raise ValueError("adamw_ema_step_guarded_dev_: ema / p / nlive sizes disagree")
+    call("ubpl_adamw_ema_step_guarded_dev", p, g, m, v, int(nlive), float(lr), float(beta1), float(beta2),
+         float(eps), float(weight_decay), step_t, coef, ema, p.numel(), float(alpha), guard, skipped)
+
+
+def restore_if_(dst, saved, guard):
+    """dst = saved when guard[2] is set; otherwise nothing."""
+    _chk(dst, "dst")
+    _chk(saved, "saved")
+    if dst.numel() != saved.numel():
+        raise ValueError("restore_if_: dst and saved sizes disagree")
+    call("ubpl_restore_if", dst, saved, dst.numel(), guard)
+
+
 # ------------------------------------------------------------------ BN
 def bn_part(B, C, device):
     """Zeroed BN scratch (partial sums + self-resetting arrival counters)."""

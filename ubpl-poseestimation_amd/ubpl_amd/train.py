@@ -391,19 +391,122 @@ def _drive(gen):
 _FUSED_EMA = os.environ.get("UBPL_FUSED_EMA", "1") != "0"
 
 
+# ---------------------------------------------------------------------------
+# guarded step: args.maxGradNorm (0 / absent: off), args.skipNonFinite (absent:
+# False), args.maxSkippedSteps (default 10) — DESIGN.md §4
+# ---------------------------------------------------------------------------
+# Order within a step: backward, the gradient all-reduce (every rank then holds
+# the same summed gradients and takes the same decision), the guard, the guarded
+# step.  With skipNonFinite each network's BatchNorm running statistics are
+# copied to a shadow buffer at the start of the step and put back after the
+# guard when the step is skipped: student i and teacher i by student i's guard
+# (a NaN teacher output reaches student i's consistency loss).  Everything goes
+# through device memory, inside the captured region.
+def _guard_opts(args):
+    return (float(getattr(args, "maxGradNorm", 0) or 0), bool(getattr(args, "skipNonFinite", False)),
+            int(getattr(args, "maxSkippedSteps", 10)))
+
+
+def _guard_nets(models, models_ema):
+    """Per optimizer, the networks whose BatchNorm statistics its guard covers."""
+    return [[m] + ([models_ema[i]] if i < len(models_ema) else []) for i, m in enumerate(models)]
+
+
+def _bn_shadows(o, nets):
+    sh = getattr(o, "_bn_shadow", None)
+    if sh is None or [s.shape for s in sh] != [n.flat_stats.shape for n in nets]:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("ubpl_amd.train: the BatchNorm shadow buffers must exist before the step is captured")
+        sh = o._bn_shadow = [torch.empty_like(n.flat_stats) for n in nets]
+    return sh
+
+
+def _configure_guard(optims, nets, args):
+    """Apply args' guard options to the optimizers (an optimizer built with its own
+    options keeps them when args sets none) and allocate the shadow buffers."""
+    mgn, snf, _ = _guard_opts(args)
+    for o, ns in zip(optims, nets):
+        if mgn > 0 or snf:
+            if not hasattr(o, "configure_guard"):
+                raise TypeError("ubpl_amd.train: maxGradNorm / skipNonFinite need FlatAdamW optimizers, got %s "
+                                "(torch's AdamW is not covered)" % type(o).__name__)
+            if (o.max_grad_norm, o.skip_nonfinite) != (mgn, snf):
+                o.configure_guard(mgn, snf)
+        if getattr(o, "skip_nonfinite", False):
+            _bn_shadows(o, ns)
+
+
+def _save_stats(optims, nets):
+    """Start of a step: shadow copies of the BatchNorm running statistics."""
+    for o, ns in zip(optims, nets):
+        if getattr(o, "skip_nonfinite", False):
+            for s, n in zip(_bn_shadows(o, ns), ns):
+                s.copy_(n.flat_stats)
+
+
+def _guard_and_restore(optims, nets):
+    """After the gradients are final: each guarded optimizer's guard, then the
+    statistics of a skipped step back from their shadows."""
+    for o, ns in zip(optims, nets):
+        if not getattr(o, "guarded", False):
+            continue
+        g = o.guard()
+        if o.skip_nonfinite:
+            for s, n in zip(_bn_shadows(o, ns), ns):
+                Kn.restore_if_(n.flat_stats, s, g)
+
+
+def _gd(o):
+    return {"guard_done": True} if getattr(o, "guarded", False) else {}
+
+
+class _SkipWatch:
+    """The consecutive-skip counts reach the host as the records do, one step late
+    (a second small lagged copy: no new host synchronisation per step); at
+    maxSkippedSteps in a row the run stops with FloatingPointError."""
+
+    def __init__(self, optims, args):
+        self.optims = [o for o in optims if getattr(o, "guarded", False)]
+        self.limit = _guard_opts(args)[2]
+        self.lag = _LaggedRecords()
+
+    def push(self, bat):
+        if self.optims and self.limit > 0:
+            self.lag.push(torch.stack([o._skipped for o in self.optims]), lambda host, bat=bat: self._check(host, bat))
+
+    def _check(self, host, bat):
+        worst = max(int(c) for c in host[1::2])
+        if worst >= self.limit:
+            raise FloatingPointError(
+                "ubpl_amd.train: %d consecutive optimizer steps skipped for a non-finite gradient (batch %d; "
+                "totals per student: %s).  The default 2xfp16 conv path holds its operands in fp16 after "
+                "power-of-two scaling: |activation| <= 2047 and |w| <= 65504 / fp16_wscale(K) (K = Cin * taps; "
+                "|w| <= 4 for a 64-channel 3x3); beyond that range the forward overflows to inf and the "
+                "gradients to NaN.  Check the inputs for inf / NaN, lower the learning rate or set maxGradNorm, "
+                "or run with UBPL_CONV_PRECISION=6xbf16, which has f32's range."
+                % (worst, bat + 1, [int(c) for c in host[0::2]]))
+
+    @contextlib.contextmanager
+    def flushing(self):
+        with self.lag.flushing():
+            yield self
+
+
 def _step_and_ema(models, models_ema, optims, args):
     """optims[i].step() for every student, then update_ema_variables(student,
     teacher) (projects/MT_UBPL.py:338-344, DualPose_UBPL.py:281-287); the
     teacher of model i depends only on student i's updated weights, so the
-    per-model fused pass gives the same bits."""
+    per-model fused pass gives the same bits.  Guarded optimizers first take
+    their guard and restore a skipped step's BatchNorm statistics."""
     from .parameters import ema_alpha
+    _guard_and_restore(optims, _guard_nets(models, models_ema))
     if _FUSED_EMA and all(hasattr(o, "step_and_ema") and o.model is m for o, m in zip(optims, models)):
         a = ema_alpha(args.epo, args.ema_decay)
         for o, e in zip(optims, models_ema):
-            o.step_and_ema(e, a)
+            o.step_and_ema(e, a, **_gd(o))
         return
     for o in optims:
-        o.step()
+        o.step(**_gd(o))
     for mi, m in enumerate(models):
         update_ema_variables(m, models_ema[mi], args)
 
@@ -580,7 +683,8 @@ class _StepGraph:
         and its memory pool are released and the next step re-captures."""
         key = (core.__name__, tuple(map(id, models)), tuple(map(id, models_ema)), tuple(map(id, optims)))
         hkey = (repr(sorted(vars(args).items())) if hasattr(args, "__dict__") else repr(args),
-                repr([o.param_groups for o in optims]))
+                repr([(o.param_groups, getattr(o, "max_grad_norm", None), getattr(o, "skip_nonfinite", None))
+                      for o in optims]))
         r = cls._cache.get(key)
         if r is None:
             cls.clear()                      # one runner: an old one would pin its networks and pool
@@ -693,6 +797,7 @@ def _mt_ubpl_core(models, models_ema, optims, args, augs_imgMap, augs_heatmaps, 
     S = args.nStack
     for o in optims:
         o.zero_grad()
+    _save_stats(optims, _guard_nets(models, models_ema))
     A = len(augs_imgMap)
     imgs = [x.to(dev, non_blocking=True).float().contiguous() for x in augs_imgMap]
     hms, gates = _targets(imgs, augs_heatmaps, meta, A, dev, args)
@@ -864,19 +969,23 @@ def train_mt_ubpl(trainLoader, models, models_ema, optims, args, verbose=True):
         m.train()
     for e in models_ema:
         e.train()
+    _configure_guard(optims, _guard_nets(models, models_ema), args)
     runner = _StepGraph.get(_mt_ubpl_core, models, models_ema, optims, args)
     lag = _LaggedRecords()
-    with lag.flushing():
+    watch = _SkipWatch(optims, args)
+    with lag.flushing(), watch.flushing():
         for bat, (augs_imgMap, augs_heatmaps, meta) in enumerate(trainLoader):
             packed, meta_h = runner.run((augs_imgMap, augs_heatmaps, meta), dev)
+            watch.push(bat)
             # the step's one device->host copy, read after the next step is enqueued
             lag.push(packed, lambda host, bat=bat, meta_h=meta_h: _mt_ubpl_records(
-                host, bat, meta_h, M, pec_c, mtc_c, epc_c, fdc_c, args, verbose))
+                host, bat, meta_h, M, pec_c, mtc_c, epc_c, fdc_c, args, verbose, bool(watch.optims)))
     return ([c.avg for c in pec_c], [c.avg for c in mtc_c], [c.avg for c in epc_c], fdc_c.avg)
 
 
-def _mt_ubpl_records(host, bat, meta_h, M, pec_c, mtc_c, epc_c, fdc_c, args, verbose):
-    """One MT_UBPL step's host records -> the AvgCounters and the batch line."""
+def _mt_ubpl_records(host, bat, meta_h, M, pec_c, mtc_c, epc_c, fdc_c, args, verbose, guarded=False):
+    """One MT_UBPL step's host records -> the AvgCounters and the batch line.
+    guarded: a step without pseudo labels prints a nan rate (see _pseudo_rate)."""
     nf, mtc_n, B, ncn, use_ep = meta_h
     nrec = 3 * M + 1
     for mi in range(M):
@@ -894,7 +1003,7 @@ def _mt_ubpl_records(host, bat, meta_h, M, pec_c, mtc_c, epc_c, fdc_c, args, ver
         # the reference's batch line divides by the pseudo-label count whether or not it
         # prints anywhere (projects/MT_UBPL.py:292-293, integer counts): a step with none
         # raises ZeroDivisionError there, and here when its records are consumed
-        rate = _pseudo_rate(n_sel, n_ps)
+        rate = _pseudo_rate(n_sel, n_ps, guarded)
         if verbose:
             sc = host[nrec + ncn:]
             print("batch.{} (scoreThr:{}): {} ({}/{}), pseudo-score: [{}]".format(
@@ -903,10 +1012,14 @@ def _mt_ubpl_records(host, bat, meta_h, M, pec_c, mtc_c, epc_c, fdc_c, args, ver
                 ", ".join(format(v, ".3f") for v in sc)))
 
 
-def _pseudo_rate(n_sel, n_ps):
+def _pseudo_rate(n_sel, n_ps, guarded=False):
     """n_sel / n_ps as the reference's batch line computes it: Python ints, so a step
     without pseudo labels raises ZeroDivisionError (projects/MT_UBPL.py:292-293,
-    DualPose_UBPL.py:212-213,238-239)."""
+    DualPose_UBPL.py:212-213,238-239).  guarded (the optimizers run under the
+    non-finite guard): nan instead — a poisoned batch counts no pseudo label, and its
+    step is skipped and counted rather than ending the run here."""
+    if guarded and int(n_ps) == 0:
+        return float("nan")
     return int(n_sel) / int(n_ps)
 
 
@@ -932,6 +1045,7 @@ def _dualpose_core(models, models_ema, optims, args, stu_imgMap, stu_heatmap, em
     S = args.nStack
     for o in optims:
         o.zero_grad()
+    _save_stats(optims, _guard_nets(models, models_ema))
     si = stu_imgMap.to(dev, non_blocking=True).float().contiguous()
     ei = ema_imgMap.to(dev, non_blocking=True).float().contiguous()
     if stu_heatmap is None:
@@ -1025,17 +1139,22 @@ def train_dualpose_ubpl(trainLoader, models, models_ema, optims, args, verbose=T
         m.train()
     for e in models_ema:
         e.train()
+    _configure_guard(optims, _guard_nets(models, models_ema), args)
     runner = _StepGraph.get(_dualpose_core, models, models_ema, optims, args)
     lag = _LaggedRecords()
-    with lag.flushing():
+    watch = _SkipWatch(optims, args)
+    with lag.flushing(), watch.flushing():
         for bat, (stu_imgMap, stu_heatmap, ema_imgMap, meta) in enumerate(trainLoader):
             packed, (ncn, K, use_ep, nfd) = runner.run((stu_imgMap, stu_heatmap, ema_imgMap, meta), dev)
+            watch.push(bat)
             lag.push(packed, lambda host, bat=bat, ncn=ncn, K=K, use_ep=use_ep, nfd=nfd: _dualpose_records(
-                host, bat, ncn, K, use_ep, nfd, M, S, pec_c, mtc_c, epc_c, fdc_c, args, verbose))
+                host, bat, ncn, K, use_ep, nfd, M, S, pec_c, mtc_c, epc_c, fdc_c, args, verbose,
+                bool(watch.optims)))
     return ([c.avg for c in pec_c], [c.avg for c in mtc_c], [c.avg for c in epc_c], fdc_c.avg)
 
 
-def _dualpose_records(host, bat, ncn, K, use_ep, nfd, M, S, pec_c, mtc_c, epc_c, fdc_c, args, verbose):
+def _dualpose_records(host, bat, ncn, K, use_ep, nfd, M, S, pec_c, mtc_c, epc_c, fdc_c, args, verbose,
+                      guarded=False):
     """One DualPose_UBPL step's host records -> the AvgCounters and the batch lines."""
     nrec = 3 * M + 1
     cbase = nrec
@@ -1053,8 +1172,8 @@ def _dualpose_records(host, bat, ncn, K, use_ep, nfd, M, S, pec_c, mtc_c, epc_c,
     c_sel = int(sum(host[cbase + 6 * mi + 4] for mi in range(M)))
     e_ps = int(sum(host[cbase + 6 * mi + 2] for mi in range(M)))
     e_sel = int(sum(host[cbase + 6 * mi + 5] for mi in range(M)))
-    c_rate = _pseudo_rate(c_sel, c_ps)                        # (the reference's lines raise on a zero count)
-    e_rate = _pseudo_rate(e_sel, e_ps) if use_ep else None
+    c_rate = _pseudo_rate(c_sel, c_ps, guarded)               # (the reference's lines raise on a zero count)
+    e_rate = _pseudo_rate(e_sel, e_ps, guarded) if use_ep else None
     if verbose:
         print("batch.{} consist-pseudo (scoreThr:{}): {} ({}/{}), pseudo-score: [{}]".format(
             format(bat + 1, "5d"), format(args.pseudoScoreThr, ".2f"),
@@ -1078,34 +1197,41 @@ def train_mt(trainLoader, model, model_ema, optim, args):
     model.train()
     model_ema.train()
     pick = (lambda r: r) if args.feature_mode == "default" else (lambda r: r[0])
-    for bat, (augs_imgMap, augs_heatmaps, meta) in enumerate(trainLoader):
-        optim.zero_grad()
-        A = len(augs_imgMap)
-        imgs = [x.to(dev, non_blocking=True).float().contiguous() for x in augs_imgMap]
-        hms, gates = _targets(imgs, augs_heatmaps, meta, A, dev, args)
-        sw = _w(_islabeled(meta["islabeled"][0], dev), 1.0, 0.0)
-        outs, outs_ema = [], []
-        for a in range(A):
-            outs.append(pick(model(imgs[a])))
-            with torch.no_grad():
-                outs_ema.append(pick(model_ema(imgs[a])))
-        B, K = outs[0].shape[0], outs[0].shape[2]
-        sd = sum(_dist_last(outs[a], outs_ema[a])[0] for a in range(A))
-        ps = [_mse(outs[a], hms[a], S, gates[a], sw.reshape(-1, 1)) for a in range(A)]
-        sp = sum(p[0] for p in ps)
-        cp = sum(p[1][0] for p in ps)
-        counts, sums = _sync_stats(torch.stack([sd, sp]), cp.float().reshape(1))
-        mtc_n = A * B * K * D.world()
-        mtc = args.consWeight * (sd / mtc_n)
-        pec = args.poseWeight * _norm(sp, counts[0])
-        (pec + mtc).backward()
-        D.allreduce_grads([model])
-        optim.step()
-        update_ema_variables(model, model_ema, args)
-        host = torch.stack([args.poseWeight * _norm(sums[1], counts[0]), args.consWeight * sums[0] / mtc_n,
-                            counts[0]]).cpu().tolist()
-        mtc_c.update(host[1], mtc_n)
-        pec_c.update(host[0], int(host[2]))
+    nets = _guard_nets([model], [model_ema])
+    _configure_guard([optim], nets, args)
+    watch = _SkipWatch([optim], args)
+    with watch.flushing():
+        for bat, (augs_imgMap, augs_heatmaps, meta) in enumerate(trainLoader):
+            optim.zero_grad()
+            _save_stats([optim], nets)
+            A = len(augs_imgMap)
+            imgs = [x.to(dev, non_blocking=True).float().contiguous() for x in augs_imgMap]
+            hms, gates = _targets(imgs, augs_heatmaps, meta, A, dev, args)
+            sw = _w(_islabeled(meta["islabeled"][0], dev), 1.0, 0.0)
+            outs, outs_ema = [], []
+            for a in range(A):
+                outs.append(pick(model(imgs[a])))
+                with torch.no_grad():
+                    outs_ema.append(pick(model_ema(imgs[a])))
+            B, K = outs[0].shape[0], outs[0].shape[2]
+            sd = sum(_dist_last(outs[a], outs_ema[a])[0] for a in range(A))
+            ps = [_mse(outs[a], hms[a], S, gates[a], sw.reshape(-1, 1)) for a in range(A)]
+            sp = sum(p[0] for p in ps)
+            cp = sum(p[1][0] for p in ps)
+            counts, sums = _sync_stats(torch.stack([sd, sp]), cp.float().reshape(1))
+            mtc_n = A * B * K * D.world()
+            mtc = args.consWeight * (sd / mtc_n)
+            pec = args.poseWeight * _norm(sp, counts[0])
+            (pec + mtc).backward()
+            D.allreduce_grads([model])
+            _guard_and_restore([optim], nets)
+            optim.step(**_gd(optim))
+            update_ema_variables(model, model_ema, args)
+            watch.push(bat)
+            host = torch.stack([args.poseWeight * _norm(sums[1], counts[0]), args.consWeight * sums[0] / mtc_n,
+                                counts[0]]).cpu().tolist()
+            mtc_c.update(host[1], mtc_n)
+            pec_c.update(host[0], int(host[2]))
     return pec_c.avg, mtc_c.avg
 
 
@@ -1115,19 +1241,26 @@ def train_supervised(trainLoader, model, optim, args):
     dev = model.flat_params.device
     model.train()
     pick = (lambda r: r) if args.feature_mode == "default" else (lambda r: r[0])
-    for bat, (imgMap, heatmap, meta) in enumerate(trainLoader):
-        optim.zero_grad()
-        img = imgMap.to(dev, non_blocking=True).float().contiguous()
-        hm = heatmap.to(dev, non_blocking=True).float().contiguous()
-        out = pick(model(img))
-        s, c = _mse_plain(out, hm, args.nStack)
-        counts, sums = _sync_stats(s.reshape(1), c[0].float().reshape(1))
-        pec = args.poseWeight * _norm(s, counts[0])
-        pec.backward()
-        D.allreduce_grads([model])
-        optim.step()
-        host = torch.stack([args.poseWeight * _norm(sums[0], counts[0]), counts[0]]).cpu().tolist()
-        pec_c.update(host[0], int(host[1]))
+    nets = _guard_nets([model], [])
+    _configure_guard([optim], nets, args)
+    watch = _SkipWatch([optim], args)
+    with watch.flushing():
+        for bat, (imgMap, heatmap, meta) in enumerate(trainLoader):
+            optim.zero_grad()
+            _save_stats([optim], nets)
+            img = imgMap.to(dev, non_blocking=True).float().contiguous()
+            hm = heatmap.to(dev, non_blocking=True).float().contiguous()
+            out = pick(model(img))
+            s, c = _mse_plain(out, hm, args.nStack)
+            counts, sums = _sync_stats(s.reshape(1), c[0].float().reshape(1))
+            pec = args.poseWeight * _norm(s, counts[0])
+            pec.backward()
+            D.allreduce_grads([model])
+            _guard_and_restore([optim], nets)
+            optim.step(**_gd(optim))
+            watch.push(bat)
+            host = torch.stack([args.poseWeight * _norm(sums[0], counts[0]), counts[0]]).cpu().tolist()
+            pec_c.update(host[0], int(host[1]))
     return pec_c.avg
 
 
