@@ -574,8 +574,8 @@ def test_zero_pseudo_count_raises_like_the_reference():
     def mt(n_ps, verbose):
         nrec = 3 * M + 1
         host = [0.1] * nrec + [4, n_ps, 0] * M + [2] + [0.5] * K     # per model [pec_n, epc_n, n_sel], 1 FDL view
-        T._mt_ubpl_records(host, 0, (1, 64, 4, 3 * M + 1, True), M, cnt(), cnt(), cnt(), AvgCounter(), args,
-                           verbose)
+        T._mt_ubpl_records(host, 0, T._RecordLayout(M, T._MT_UBPL_COUNTS, 1, K), 64, 4, True,
+                           (cnt(), cnt(), cnt(), AvgCounter()), args, verbose)
     for verbose in (False, True):
         with pytest.raises(ZeroDivisionError):
             mt(0, verbose)
@@ -585,7 +585,8 @@ def test_zero_pseudo_count_raises_like_the_reference():
     def dual(c_ps, verbose):
         nrec = 3 * M + 1
         host = [0.1] * nrec + [4, 4, 5, c_ps, 1, 2] * M + [2] + [0.5] * (2 * K)
-        T._dualpose_records(host, 0, 6 * M + 1, K, True, 1, M, 4, cnt(), cnt(), cnt(), AvgCounter(), args, verbose)
+        T._dualpose_records(host, 0, T._RecordLayout(M, T._DUALPOSE_COUNTS, 1, K, blocks=2), True, 4,
+                            (cnt(), cnt(), cnt(), AvgCounter()), args, verbose)
     for verbose in (False, True):
         with pytest.raises(ZeroDivisionError):
             dual(0, verbose)

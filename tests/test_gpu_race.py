@@ -112,7 +112,10 @@ def test_network_phases_enqueue_no_torch_arithmetic(case, monkeypatch):
     from ubpl_amd.optim import FlatAdamW
     monkeypatch.setenv("UBPL_MODEL_STREAMS", "1")
     monkeypatch.setenv("UBPL_STEP_GRAPH", "0")
-    monkeypatch.setattr(T, "_STREAM_CHECK", True)
+    from ubpl_amd import streams
+    monkeypatch.setattr(streams, "_STREAM_CHECK", True)            # the module whose fork() reads it
+    entered = []
+    monkeypatch.setattr(streams, "_PhaseCheck", lambda *a, **k: (entered.append(1), T._PhaseCheck(*a, **k))[1])
     cfg = seeds.step_cases()[case]
     models, emas, _ = seeds.step_models(lambda k, s, m: StackedHourglass(k, s, m), cfg, device="cuda")
     optims = [FlatAdamW(m, lr=cfg["lr"], weight_decay=0) for m in models]
@@ -121,3 +124,4 @@ def test_network_phases_enqueue_no_torch_arithmetic(case, monkeypatch):
     with contextlib.redirect_stdout(io.StringIO()):
         train(loader, models, emas, optims, args)
     torch.cuda.synchronize()
+    assert len(entered) >= 2, entered                              # the forwards' phase and the backwards'

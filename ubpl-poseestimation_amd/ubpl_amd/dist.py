@@ -25,7 +25,7 @@ import torch
 import torch.distributed as dist
 
 # UBPL_DIST_WORLD1=1: the distributed step (its two collectives, the segmented capture of
-# train._StepGraph) also on a one-rank process group — how the RCCL path is exercised on a
+# step_graph._StepGraph) also on a one-rank process group — how the RCCL path is exercised on a
 # one-GPU box (tests/test_gpu_dist.py; RCCL refuses two ranks on one device)
 _WORLD1 = os.environ.get("UBPL_DIST_WORLD1") == "1"
 

@@ -1,0 +1,195 @@
+"""Device-count loss helpers of the training steps (same row semantics as
+ubpl_amd.losses): every loss sum and every count stays a device tensor.  The loss
+section of each train.py step (between the networks' forwards and the backward)
+builds its sums, counts and FDL views from these; _RecordLayout says where they go."""
+import torch
+
+from .losses import _RowLoss, features_cov
+from .process import render_batch
+
+
+def _mse(preds, gts, S, gate, sw):
+    """JointMSELoss(nStack=S, useKPsGate=True, useSampleWeight=True): (sum, cnt[4])."""
+    K = preds.shape[2]
+    HW = preds.shape[-1] * preds.shape[-2]
+    spec = (0, S, K, HW, (K * HW, 0, 0, 1), gate is not None, sw is not None, 0.0)
+    s, c, _ = _RowLoss.apply(preds, gts, spec, gate, sw)
+    return s, c
+
+
+def _mse_plain(preds, gts, S):
+    """JointMSELoss(nStack=S) without gate/weights (projects/supervised.py:138);
+    nStack == 1 keeps the reference's per-sample rows (reshape((bs, k, -1)))."""
+    B = preds.shape[0]
+    if S == 1:
+        K = preds.shape[1]
+        HW = preds.numel() // (B * K)
+        spec = (0, 1, K, HW, (K * HW, 0, 0, 1), False, False, 0.0)
+    else:
+        K = preds.shape[2]
+        HW = preds.shape[-1] * preds.shape[-2]
+        spec = (0, S, K, HW, (K * HW, 0, 0, 1), False, False, 0.0)
+    s, c, _ = _RowLoss.apply(preds, gts, spec, None, None)
+    return s, c
+
+
+def _dist_last(preds, tpreds):
+    """JointDistLoss() on the last stack of both (projects/MT_UBPL.py:250)."""
+    a = preds[:, -1].contiguous()
+    t = tpreds[:, -1].contiguous()
+    K = a.shape[1]
+    HW = a.shape[-1] * a.shape[-2]
+    spec = (0, 1, K, HW, (K * HW, K * HW, 0, 1), False, False, 0.0)
+    s, c, _ = _RowLoss.apply(a, t, spec, None, None)
+    return s, c
+
+
+def _dist_mt2_last(preds, tpreds, sw, thr):
+    """JointDistLoss_mt2(useSampleWeight=True, scoreThr) on the last stacks
+    (projects/DualPose_UBPL.py:163,203)."""
+    a = preds[:, -1].contiguous()
+    t = tpreds[:, -1].contiguous()
+    K = a.shape[1]
+    HW = a.shape[-1] * a.shape[-2]
+    spec = (1, 1, K, HW, (K * HW, K * HW, 0, 1), False, True, float(thr))
+    return _RowLoss.apply(a, t, spec, None, sw)
+
+
+def _pseudo(preds, targets, sw, S, thr):
+    """JointPseudoLoss3(nStack=S, scoreThr) with targets [M,B,S,K,R,R]."""
+    B, K = preds.shape[0], preds.shape[2]
+    HW = preds.shape[-1] * preds.shape[-2]
+    M, St = targets.shape[0], targets.shape[2]
+    spec = (2, S, K, HW, (St * K * HW, 0, B * St * K * HW, M, (St - 1) * K * HW), False, True, float(thr))
+    return _RowLoss.apply(preds, targets, spec, None, sw)
+
+
+def _norm(s, n):
+    """(s / n) if n > 0 else s — with n a device tensor."""
+    n = n.float()
+    return torch.where(n > 0, s / n.clamp(min=1.0), s)
+
+
+def _fdl_view(fa, fb, rowmask, args):
+    """One view of the multi-view feature decorrelation term (projects/MT_UBPL.py:
+    301-330, DualPose_UBPL.py:246-270) over the selected rows (rowmask > 0):
+    returns (kind, value, n_loc) with n_loc a device float[1].
+
+    'covariance' (FDL_type default): value = ProcessUtils.features_cov of the
+    selected rows = their MEAN |cov| (0 when no row of this rank is selected),
+    n_loc = rows * S * C.  Any other FDL_type: the reference's else branch,
+    JointFeatureDistLoss (utils/losses.py:56-70): value = SUM over the selected
+    (sample, stack, channel) rows of the pixel-mean squared distance, n_loc =
+    rows * S.  The value of a covariance view is a mean, so under data
+    parallelism _fdl_total rescales it by n_loc / N_glob before summing."""
+    if args.FDL_type == "covariance":
+        v, c = features_cov(fa, fb, rowmask)
+        n = c.float()
+        return "cov", torch.where(n[0] > 0, v, torch.zeros_like(v)), n
+    B, S, C = fa.shape[:3]
+    HW = fa[0, 0, 0].numel()
+    spec = (0, 1, S * C, HW, (S * C * HW, 0, 0, 1), False, True, 0.0)
+    s, _, _ = _RowLoss.apply(fa.contiguous(), fb.contiguous(), spec, None, rowmask.reshape(-1).contiguous())
+    return "dist", s, ((rowmask > 0).sum() * S).float().reshape(1)
+
+
+def _fdl_total(views, gcounts_v, W, weight):
+    """fdc = FDLWeight * (sum_a value_a) / (sum_a N_a) with global counts N_a
+    (MT_UBPL.py:329).  A covariance view is a mean over this rank's rows;
+    value_a * n_loc_a / N_a is its share of the global-batch mean (exactly
+    value_a on one rank), so the SUM all-reduce of the gradients gives the
+    single-device gradient."""
+    terms = []
+    for (kind, v, n_loc), N_a in zip(views, gcounts_v):
+        if kind == "cov" and W > 1:
+            v = v * (n_loc[0] / N_a.clamp(min=1.0))
+        terms.append(v)
+    return weight * _norm(sum(terms), sum(gcounts_v))
+
+
+def _fdl_record_sums(views):
+    """What each rank contributes to the all-reduced FDL record: the local
+    SUM (covariance: mean * rows)."""
+    return [v.detach() * n[0] if kind == "cov" else v.detach() for kind, v, n in views]
+
+
+def _fdl_record(views, gsums_v, gcounts_v, W, weight):
+    if W == 1:
+        vals = [v.detach() for _, v, _ in views]
+    else:
+        vals = [s / N.clamp(min=1.0) if kind == "cov" else s
+                for (kind, _, _), s, N in zip(views, gsums_v, gcounts_v)]
+    return weight * _norm(sum(vals), sum(gcounts_v))
+
+
+def _fdl_rows(sw, args):
+    if args.FDL_label == "labeled":
+        return (sw > 0).float()
+    if args.FDL_label == "unlabeled":
+        return (sw == 0).float()
+    return torch.ones_like(sw)
+
+
+def _islabeled(meta_isl, dev):
+    return meta_isl.to(dev, non_blocking=True).reshape(-1)
+
+
+def _w(isl, lab, unlab):
+    one = torch.ones(isl.shape[0], device=isl.device)
+    return torch.where(isl > 0, lab * one, unlab * one).contiguous()
+
+
+def _targets(imgs, hms, meta, A, dev, args):
+    """Heatmaps and gates per view: either given (reference batch format) or
+    rendered on the device from meta['kps'] (list of [B,K,3] per view)."""
+    if hms is not None:
+        hs = [h[0].to(dev, non_blocking=True).float().contiguous() for h in hms]
+        gs = [kw[0].to(dev, non_blocking=True).float().contiguous() for kw in meta["kpsWeights"]]
+        return hs, gs
+    hs, gs = [], []
+    inp = imgs[0].shape[-1]
+    for a in range(A):
+        hm, kk = render_batch(meta["kps"][a].to(dev).float(), (imgs[a].shape[-2], imgs[a].shape[-1]), inp,
+                              args.outRes if hasattr(args, "outRes") else inp // 4)
+        hs.append(hm)
+        gs.append(kk[:, :, 2].contiguous())
+    return hs, gs
+
+
+class _RecordLayout:
+    """Where everything sits in a generator step's three vectors — the only
+    place that knows offsets; the cores pack by it, the decoders read by it.
+      sums (local / all-reduced): per model SUMS, then one per FDL view
+      counts:                     per model `counts`, then one per FDL view
+      packed (the one device->host copy): [3M+1 records: per model RECS, then fdc | counts | `blocks` x K scores]
+    A plain host object (no tensors): built when the step is captured and reused at every replay."""
+    SUMS = ("mtc", "pec", "epc")
+    RECS = ("pec", "mtc", "epc")
+
+    def __init__(self, M, counts, nfd, K, blocks=1):
+        self.M, self.counts, self.nfd, self.K = M, tuple(counts), nfd, K
+        nc = len(self.counts) * M
+        self.nrec, self.ncn = 3 * M + 1, nc + nfd
+        self.size = self.nrec + self.ncn + blocks * K
+        self.fdc = 3 * M                                              # in packed: the FDL record
+        self.fdl_sums = slice(3 * M, 3 * M + nfd)                     # in sums: the FDL views
+        self.fdl_counts = slice(nc, nc + nfd)                         # in counts
+        self.fdl_n = slice(self.nrec + nc, self.nrec + nc + nfd)      # in packed
+
+    def s(self, name, mi):                    # in sums: model mi's sum `name`
+        return 3 * mi + self.SUMS.index(name)
+
+    def c(self, name, mi):                    # in counts: model mi's count `name`
+        return len(self.counts) * mi + self.counts.index(name)
+
+    def r(self, name, mi):                    # in packed: model mi's record `name`
+        return 3 * mi + self.RECS.index(name)
+
+    def n(self, name, mi):                    # in packed: model mi's count `name`
+        return self.nrec + self.c(name, mi)
+
+    def total(self, host, name):              # of packed.tolist(): the count `name` summed over the models
+        return int(sum(host[self.n(name, mi)] for mi in range(self.M)))
+
+    def scores(self, block=0):                # in packed: score block `block`
+        return slice(self.nrec + self.ncn + block * self.K, self.nrec + self.ncn + (block + 1) * self.K)
