@@ -124,6 +124,44 @@ int ubpl_decode_heatmaps_flip(const float* hm, const float* hm_flip, int64_t sb,
 int ubpl_ensemble_pseudo(const float* hm, int64_t sm, int64_t sb, int M, int N, int K, int H, int W,
                          const double* tinv, const float* thr, float* mean_hm, float* ens_raw, float* ens_preds,
                          float* ens_score, float* member_score, float* disagree, float* select, void* stream);
+/* Sub-pixel refinement of decoded peaks, a post-pass after any of the decodes
+ * above.  hm, hm_flip, sb and perm as in ubpl_decode_heatmaps_flip; the value
+ * at (y, x) of map (n, k) is v(y,x) = (hm[..] + hm_flip[n,perm[k],y,W-1-x]) *
+ * 0.5f (hm_flip null: hm[..]) — the decode's own expression — and 0 outside
+ * the map.  raw [N,K,2]: the 1-based integer peaks the decode wrote, (0,0) =
+ * no peak.  mode 1 = quarter, 2 = Taylor (anything else:
+ * hipErrorInvalidValue).  taps: device f32 w[0..radius], the half of a
+ * symmetric separable blur kernel (radius 0, taps {1}: no blur), 0 <= radius
+ * <= 5.  Per map, with c = raw_x - 1, r = raw_y - 1; every comparison is
+ * false on a NaN, so a non-finite window only falls back:
+ *   rule 0   raw outside [1,W]x[1,H] (the (0,0) of no peak included) or not
+ *            v(r,c) > 0: how = 0, raw_sub = raw.
+ *   Taylor   (mode 2, 2 <= c <= W-3 and 2 <= r <= H-3) b(dy,dx), dy, dx in
+ *            [-2,2]: v blurred along x, then along y; each pass is w[0] x(0) +
+ *            sum_{j=1..radius} w[j] (x(-j) + x(+j)) in f32, ascending j.
+ *            L = logf(fmaxf(b, 1e-10f));
+ *            gx = (L(0,1) - L(0,-1))/2, gy = (L(1,0) - L(-1,0))/2,
+ *            dxx = (L(0,2) - 2 L(0,0) + L(0,-2))/4, dyy likewise,
+ *            dxy = (L(1,1) - L(-1,1) - L(1,-1) + L(-1,-1))/4, det = dxx dyy -
+ *            dxy^2.  If dxx < 0 and det > 0: ox = -(dyy gx - dxy gy)/det, oy =
+ *            -(dxx gy - dxy gx)/det, and if |ox| <= 1 and |oy| <= 1: how = 2.
+ *            (The distribution-aware decode; the blurred map's rescale to the
+ *            original maximum is a constant in log space and is dropped.)
+ *   quarter  (otherwise: mode 1, and the fallback of mode 2) on unblurred
+ *            values: ox = 0.25 sign(v(r,c+1) - v(r,c-1)) when 1 <= c <= W-2,
+ *            else 0; oy likewise on rows; sign(0) = sign(NaN) = 0; how = 1 if
+ *            either axis was eligible, else 0.
+ * raw_sub [N,K,2] = (raw_x + ox, raw_y + oy); preds_sub [N,K,2] = (t0 u + t1 v +
+ * t2 + 1, t3 u + t4 v + t5 + 1), u = raw_sub_x - 1, v = raw_sub_y - 1, in f64
+ * with the decode's un-fused multiply/add order, rounded to f32 and NOT
+ * truncated (the decode's preds is the truncation of this expression at ox =
+ * oy = 0); how [N,K] = the rule taken, {0, 1, 2} as floats.  tinv, preds_sub
+ * and how are nullable (preds_sub needs tinv).  No atomics, fixed summation
+ * order: repeated launches give equal bits. */
+/*@ hm:f32[(N-1)*sb+(int64_t)K*H*W] hm_flip:f32[(N-1)*sb+(int64_t)K*H*W] perm:i32[K] raw:f32[N*K*2] taps:f32[radius+1] tinv:f64[N*6] raw_sub:f32[N*K*2] preds_sub:f32[N*K*2] how:f32[N*K] */
+int ubpl_refine_peaks(const float* hm, const float* hm_flip, int64_t sb, int N, int K, int H, int W,
+                      const int* perm, const float* raw, int mode, const float* taps, int radius,
+                      const double* tinv, float* raw_sub, float* preds_sub, float* how, void* stream);
 /* EvaluationUtils.acc_pck (utils/evaluation.py:91-139).  errs/accs [K+1];
  * hits/valid [K] int32 (nullable) for cross-rank aggregation. */
 /*@ preds:f32[N*K*2] gts:f32[N*K*3] errs:f32[K+1] accs:f32[K+1] hits:i32[K] valid:i32[K] */

@@ -45,8 +45,9 @@ def main():
                       "wall_s": log["wall_s"]}))
 
 
-def run(a, write=True):
-    """The experiment of main() with options `a` (parser() defaults); returns the log."""
+def run(a, write=True, keep=None):
+    """The experiment of main() with options `a` (parser() defaults); returns the log.
+    keep: a dict that receives the trained networks ("models", "emas")."""
 
     from ubpl_amd import _lib, mouse
     from ubpl_amd import parameters as PR
@@ -122,6 +123,8 @@ def run(a, write=True):
     log["best_pck"], log["best_epoch"] = best
     log["final_pck"] = log["epochs"][-1]["pck"]
     log["wall_s"] = round(time.time() - t0, 1)
+    if keep is not None:
+        keep.update({"models": models, "emas": emas})
     if write:
         os.makedirs(os.path.dirname(a.out), exist_ok=True)
         with open(a.out, "w") as f:

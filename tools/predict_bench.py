@@ -29,6 +29,17 @@ with the flip test on:
 
 Same warm-up, rounds and report; (p) and (r) must select the same joints before anything
 is timed.
+
+--refine quarter|taylor (--blur-sigma S) builds the Predictors of either mode with the
+sub-pixel decode on.  --mode refine times what it adds, on three Predictors of the same
+teacher that differ in the option alone:
+
+  (n) none      Predictor.predict(x, center, scale) with refine="none";
+  (u) quarter   the same with refine="quarter" (one ubpl_refine_peaks launch more per replay);
+  (t) taylor    the same with refine="taylor" at --blur-sigma.
+
+Same warm-up, rounds and report; the integer outputs of the three must agree bit for bit
+before anything is timed.
 """
 import argparse
 import json
@@ -71,6 +82,58 @@ def measure(variants, a):
     return row
 
 
+def refine_kw(a):
+    """The Predictor arguments of --refine / --blur-sigma."""
+    kw = {"refine": a.refine}
+    if a.blur_sigma is not None:
+        kw["blur_sigma"] = a.blur_sigma
+    return kw if a.refine != "none" else {}
+
+
+def teacher(a, seed, gen, dev):
+    from ubpl_amd.hourglass import StackedHourglass
+    torch.manual_seed(seed)
+    m = StackedHourglass(a.k, a.stacks, "AvgPool")
+    with torch.no_grad():
+        for _ in range(2):                       # running statistics off their initial values
+            m((torch.rand(4, 3, a.res, a.res, generator=gen) - 0.5).to(dev))
+    return m.eval()
+
+
+def refine_main(a):
+    from ubpl_amd import Predictor, _lib, kernels as Kn
+    _lib.require_gpu()
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    gen = torch.Generator().manual_seed(1)
+    model = teacher(a, 0, gen, dev)
+    sg = {} if a.blur_sigma is None else {"blur_sigma": a.blur_sigma}
+    P = {"none": Predictor(model), "quarter": Predictor(model, refine="quarter"),
+         "taylor": Predictor(model, refine="taylor", **sg)}
+    rows = []
+    for B in [int(b) for b in a.batches.split(",")]:
+        x = (torch.rand(B, 3, a.res, a.res, generator=gen) - 0.5).to(dev)
+        center = torch.full((B, 2), a.res / 2.0)
+        scale = torch.full((B,), a.res / 200.0)
+        outs = {n: p.predict(x, center, scale) for n, p in P.items()}
+        for n in ("quarter", "taylor"):
+            if not all(torch.equal(outs[n][k], outs["none"][k]) for k in outs["none"]):
+                raise SystemExit("predict_bench: refine=%s changes the integer outputs at B=%d" % (n, B))
+        row = {"B": B, "taylor_rule_2_fraction": round(float((outs["taylor"]["refine_rule"] == 2).float().mean()), 4)}
+        row.update(measure({n: (lambda p=p: p.predict(x, center, scale)) for n, p in P.items()}, a))
+        for n in ("quarter", "taylor"):
+            row[n + "_added_us"] = round((row[n + "_ms"] - row["none_ms"]) * 1e3, 1)
+        rows.append(row)
+    out = {"tool": "predict_bench", "mode": "refine", "model": "HG%d" % a.stacks, "k": a.k, "res": a.res,
+           "blur_sigma": P["taylor"].blur_sigma, "precision": Kn.conv_precision_name(), "repeats": a.repeats,
+           "device": torch.cuda.get_device_name(0), "rows": rows}
+    line = json.dumps(out)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
 def pseudo_main(a):
     from ubpl_amd import Predictor, _lib, kernels as Kn
     from ubpl_amd.hourglass import StackedHourglass
@@ -87,7 +150,7 @@ def pseudo_main(a):
             for _ in range(2):                   # running statistics off their initial values
                 m((torch.rand(4, 3, a.res, a.res, generator=gen) - 0.5).to(dev))
         models.append(m.eval())
-    P = Predictor(models, flip_test=True)
+    P = Predictor(models, flip_test=True, **refine_kw(a))
     rows = []
     for B in [int(b) for b in a.batches.split(",")]:
         x = (torch.rand(B, 3, a.res, a.res, generator=gen) - 0.5).to(dev)
@@ -136,11 +199,15 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--window", type=float, default=0.25, help="seconds of work per variant per round")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--mode", default="predict", choices=["predict", "pseudo"])
+    ap.add_argument("--mode", default="predict", choices=["predict", "pseudo", "refine"])
+    ap.add_argument("--refine", default="none", choices=["none", "quarter", "taylor"])
+    ap.add_argument("--blur-sigma", type=float, default=None, help="taylor's blur (default: the Predictor's)")
     ap.add_argument("--thr", type=float, default=0.95, help="--mode pseudo: the score threshold (<= 0: each batch's median ensemble score)")
     a = ap.parse_args()
     if a.mode == "pseudo":
         return pseudo_main(a)
+    if a.mode == "refine":
+        return refine_main(a)
 
     from ubpl_amd import Predictor, _lib, kernels as Kn
     from ubpl_amd.hourglass import StackedHourglass
@@ -155,8 +222,8 @@ def main():
         for _ in range(2):                       # running statistics off their initial values
             model((torch.rand(4, 3, a.res, a.res, generator=gen) - 0.5).to(dev))
     model.eval()
-    plain = Predictor(model)
-    flip = Predictor(model, flip_test=True)
+    plain = Predictor(model, **refine_kw(a))
+    flip = Predictor(model, flip_test=True, **refine_kw(a))
     rows = []
     for B in [int(b) for b in a.batches.split(",")]:
         x = (torch.rand(B, 3, a.res, a.res, generator=gen) - 0.5).to(dev)
@@ -183,7 +250,7 @@ def main():
         rows.append(row)
     out = {"tool": "predict_bench", "model": "HG%d" % a.stacks, "k": a.k, "res": a.res,
            "precision": Kn.conv_precision_name(), "repeats": a.repeats, "device": torch.cuda.get_device_name(0),
-           "rows": rows}
+           "refine": a.refine, "rows": rows}
     line = json.dumps(out)
     if a.out:
         with open(a.out, "w") as f:

@@ -9,6 +9,15 @@ pck_thr of the truth, for the selected joints and for all of them.
 
     python tools/pseudo_label.py [--ckpt ckpts/checkpoint_best.pth.tar] [--model HG2]
                                  [--thr 0.95] [--rule unanimous|ensemble] [--flip] [--out FILE]
+                                 [--refine none|quarter|taylor|all] [--blur-sigma S]
+                                 [--train-epochs E] [--record FILE]
+
+--refine / --blur-sigma: the Predictor's sub-pixel decode (predsArraies then holds the
+sub-pixel coordinates).  --refine all labels the split once per variant — none, quarter,
+taylor at blur sigma 0, 1 and 2 — with the same weights, and --record writes, per variant, the
+PCK@pck_thr of the ensemble peak, of the teachers' mean (Predictor.validate) and the mean
+pixel error over the valid joints.  --train-epochs E: without --ckpt, train the teachers
+first by E epochs of tools/mouse_pck.py's experiment (once, shared by every variant).
 
 Reads tests/golden/mouse_100_500_0.3/ (tools/pack_mouse.py).  Untrained networks select
 next to nothing at the default threshold; that is the expected output without --ckpt.
@@ -45,16 +54,29 @@ def main():
     ap.add_argument("--inferBS", type=int, default=32)
     ap.add_argument("--limit", type=int, default=0, help="label only the first batches up to this many images")
     ap.add_argument("--out", default=os.path.join(ROOT, "build", "pseudo_labels.json"))
+    ap.add_argument("--refine", default="none", choices=["none", "quarter", "taylor", "all"])
+    ap.add_argument("--blur-sigma", type=float, default=None, help="taylor's blur (default: the Predictor's)")
+    ap.add_argument("--train-epochs", type=int, default=0, help="without --ckpt: train the teachers this long first")
+    ap.add_argument("--record", default=None, help="write the per-variant accuracy figures here")
     a = ap.parse_args()
 
     from ubpl_amd import Predictor, _lib, checkpoint, mouse
     from ubpl_amd.hourglass import pose_model
+    from ubpl_amd.predict import DEFAULT_BLUR_SIGMA
     _lib.require_gpu()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     data = mouse.MouseData.from_pack()
-    teachers = []
-    for b in range(a.teachers):
+    teachers, trained = [], None
+    if a.train_epochs > 0 and not a.ckpt:
+        sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+        import mouse_pck
+        keep = {}
+        log = mouse_pck.run(mouse_pck.parser().parse_args(["--epochs", str(a.train_epochs), "--model", a.model,
+                                                           "--valid-every", str(a.train_epochs)]), write=False, keep=keep)
+        teachers = keep["emas"][:a.teachers]
+        trained = {"epochs": a.train_epochs, "final_pck": log["final_pck"], "wall_s": log["wall_s"]}
+    for b in range(len(teachers), a.teachers):
         torch.manual_seed(b)
         teachers.append(pose_model(a.model, data.kpsCount, "AvgPool", nograd=True))
     if a.ckpt:
@@ -64,23 +86,42 @@ def main():
     loader = mouse.valid_batches(data, a.inferBS, dev)
     if a.limit:
         loader = loader[:max(1, a.limit // a.inferBS)]
-    P = Predictor(teachers, flip_test=a.flip, max_batch=a.inferBS)
-    d = P.label_pool(loader, types.SimpleNamespace(outRes=data.outRes), thr=a.thr, rule=a.rule)
-    d["source"] = {"ckpt": a.ckpt, "model": a.model, "teachers": a.teachers, "flip_test": a.flip,
-                   "split": "Mouse_100_500_0.3 valid", "images": len(d["predsArraies"])}
-    checkpoint.save_pseudo_data(d, a.out)
-
-    preds = torch.tensor(d["predsArraies"])
-    sel = torch.tensor(d["selected"])
     gts = torch.cat([m["kpsMap"] for _, _, m in loader])
-    hit, valid = within_pck(preds, gts, data.pck_ref, data.pck_thr)
-    share = lambda mask: float(hit[mask].float().mean()) if bool(mask.any()) else None
-    print(json.dumps({"out": a.out, "images": len(preds), "thr": a.thr, "rule": a.rule,
-                      "selected_fraction": round(float(sel.float().mean()), 4),
-                      "selected_fraction_per_joint": [round(v, 4) for v in d["selected_fraction"]],
-                      "within_pck_thr_all": share(valid), "within_pck_thr_selected": share(valid & sel),
-                      "trained": a.ckpt is not None}))
-
+    sigma = DEFAULT_BLUR_SIGMA if a.blur_sigma is None else a.blur_sigma
+    variants = [(a.refine, sigma)] if a.refine != "all" else \
+        [("none", sigma), ("quarter", sigma), ("taylor", 0.0), ("taylor", 1.0), ("taylor", 2.0)]
+    vargs = types.SimpleNamespace(outRes=data.outRes, pck_ref=data.pck_ref, pck_thr=data.pck_thr)
+    rows = []
+    for refine, sg in variants:
+        P = Predictor(teachers, flip_test=a.flip, max_batch=a.inferBS, refine=refine, blur_sigma=sg)
+        d = P.label_pool(loader, types.SimpleNamespace(outRes=data.outRes), thr=a.thr, rule=a.rule)
+        d["source"] = {"ckpt": a.ckpt, "model": a.model, "teachers": a.teachers, "flip_test": a.flip,
+                       "split": "Mouse_100_500_0.3 valid", "images": len(d["predsArraies"]), "trained": trained}
+        out = a.out if len(variants) == 1 else "%s.%s%s.json" % (
+            os.path.splitext(a.out)[0], refine, "_s%g" % sg if refine == "taylor" else "")
+        checkpoint.save_pseudo_data(d, out)
+        preds = torch.tensor(d["predsArraies"])
+        sel = torch.tensor(d["selected"])
+        hit, valid = within_pck(preds, gts, data.pck_ref, data.pck_thr)
+        share = lambda mask: float(hit[mask].float().mean()) if bool(mask.any()) else None
+        _, accs, _ = P.validate(loader, vargs)
+        P.release()
+        rows.append({"out": out, "refine": refine, "blur_sigma": sg if refine == "taylor" else None,
+                     "images": len(preds), "thr": a.thr, "rule": a.rule,
+                     "selected_fraction": round(float(sel.float().mean()), 4),
+                     "selected_fraction_per_joint": [round(v, 4) for v in d["selected_fraction"]],
+                     "within_pck_thr_all": share(valid), "within_pck_thr_selected": share(valid & sel),
+                     "mean_pixel_error": float((preds - gts[..., :2]).norm(dim=-1)[valid].mean()),
+                     "validate_pck": [round(v[-1], 4) for v in accs],     # teacher 1, ..., their mean
+                     "trained": a.ckpt is not None or trained is not None})
+        print(json.dumps(rows[-1]))
+    if a.record:
+        os.makedirs(os.path.dirname(os.path.abspath(a.record)), exist_ok=True)
+        with open(a.record, "w") as f:
+            json.dump({"tool": "pseudo_label", "split": "Mouse_100_500_0.3 valid", "model": a.model,
+                       "teachers": a.teachers, "flip_test": a.flip, "ckpt": a.ckpt, "training": trained,
+                       "pck_thr": data.pck_thr, "pck_ref": data.pck_ref, "variants": rows}, f, indent=1)
+            f.write("\n")
 
 if __name__ == "__main__":
     main()

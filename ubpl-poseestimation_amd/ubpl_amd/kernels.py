@@ -4,6 +4,7 @@ Each wrapper validates device / dtype / contiguity, allocates outputs with
 the torch caching allocator on the input's device and enqueues on torch's
 current stream.  Nothing here computes on the host.
 """
+import math
 import os
 
 import torch
@@ -238,6 +239,67 @@ def ensemble_pseudo(hm, sm, sb, M, N, K, H, W, thr, tinv=None, want_mean=False, 
     call("ubpl_ensemble_pseudo", hm, int(sm), int(sb), M, N, K, H, W, tinv, thr, mean_hm, ens_raw, ens_preds, ens_score,
          member_score, disagree, select)
     return ens_raw, ens_preds, ens_score, member_score, disagree, select, mean_hm
+
+
+REFINE_MODES = {"quarter": 1, "taylor": 2}
+MAX_BLUR_RADIUS = 5
+
+
+def blur_taps(sigma):
+    """Host float32 [radius + 1]: the half w[0..radius] of the Gaussian blur kernel of
+    ubpl_refine_peaks' Taylor mode.  sigma <= 0: [1.0] (no blur).  Otherwise radius =
+    ceil(2.5 sigma), w[j] = exp(-j^2 / (2 sigma^2)) normalised so that the full
+    2 radius + 1 kernel sums to 1, in float64 rounded to float32.  ValueError above
+    radius 5 (sigma > 2.0)."""
+    sigma = float(sigma)
+    if not sigma > 0:
+        return torch.ones(1, dtype=F32)
+    radius = int(math.ceil(2.5 * sigma))
+    if radius > MAX_BLUR_RADIUS:
+        raise ValueError("ubpl_amd: blur sigma %g needs radius %d, at most %d (sigma <= 2.0)"
+                         % (sigma, radius, MAX_BLUR_RADIUS))
+    w = [math.exp(-j * j / (2.0 * sigma * sigma)) for j in range(radius + 1)]
+    total = w[0] + 2.0 * sum(w[1:])
+    return torch.tensor([v / total for v in w], dtype=torch.float64).to(F32)
+
+
+def refine_peaks(hm, hm_flip, sb, N, K, H, W, perm, raw, mode, taps, tinv=None, out=None):
+    """Sub-pixel refinement of decoded peaks (ubpl_refine_peaks): hm / hm_flip / sb / perm
+    exactly as given to decode_heatmaps_flip, raw [N,K,2] the peaks it wrote.  mode
+    "quarter" or "taylor" (or 1 / 2); taps: device float32 [radius + 1]
+    (blur_taps(sigma).to(device); read in Taylor mode).
+    -> (raw_sub [N,K,2], preds_sub [N,K,2] or None, how [N,K] = the rule taken, 0 / 1 / 2);
+    out = the same tuple: write into these instead of allocating."""
+    mode = REFINE_MODES.get(mode, mode)
+    if mode not in (1, 2):
+        raise ValueError("ubpl_amd: refine mode is one of %s, got %r" % (", ".join(REFINE_MODES), mode))
+    for t, nm in ((hm, "hm"), (hm_flip, "hm_flip")):
+        if t is None:
+            continue
+        _chk(t, nm)
+        if t.numel() < (N - 1) * sb + K * H * W:
+            raise ValueError("ubpl_amd: %s holds %d floats, %d maps of stride %d need %d"
+                             % (nm, t.numel(), N, sb, (N - 1) * sb + K * H * W))
+    _chk(perm, "perm", torch.int32)
+    _chk(raw, "raw")
+    _chk(taps, "taps")
+    _chk(tinv, "tinv", torch.float64)
+    if perm is not None and perm.numel() != K:
+        raise ValueError("ubpl_amd: perm has %d entries for %d joints" % (perm.numel(), K))
+    if raw is None or raw.numel() != N * K * 2:
+        raise ValueError("ubpl_amd: raw is the decode's [N,K,2] peaks")
+    if taps is None or not 1 <= taps.numel() <= MAX_BLUR_RADIUS + 1:
+        raise ValueError("ubpl_amd: taps holds 1 to %d floats (blur_taps)" % (MAX_BLUR_RADIUS + 1))
+    dev = hm.device
+    if out is not None:
+        raw_sub, preds_sub, how = out
+    else:
+        raw_sub = torch.empty((N, K, 2), device=dev, dtype=F32)
+        preds_sub = torch.empty((N, K, 2), device=dev, dtype=F32) if tinv is not None else None
+        how = torch.empty((N, K), device=dev, dtype=F32)
+    call("ubpl_refine_peaks", hm, hm_flip, int(sb), N, K, H, W, perm, raw, mode, taps, taps.numel() - 1, tinv,
+         raw_sub, preds_sub, how)
+    return raw_sub, preds_sub, how
 
 
 def fliplr(x, out=None):

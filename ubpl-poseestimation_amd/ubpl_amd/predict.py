@@ -26,6 +26,12 @@ which joints do the networks agree on confidently enough to use as labels
 same replay with one more launch, ubpl_ensemble_pseudo, over the networks'
 merged heatmaps; `label_pool` runs it over a loader.
 
+`Predictor(refine="quarter" | "taylor")` adds sub-pixel coordinates beside the integer
+ones: after each network's decode one ubpl_refine_peaks launch on the same heatmap views
+(the quarter-offset step the reference carries commented out, utils/udaap/evaluation.py:
+218-228, or the distribution-aware Taylor step), inside the same graph.  The default
+"none" launches and returns exactly what it did without the option.
+
 There is no CPU fallback.
 """
 import os
@@ -41,7 +47,7 @@ class _Slot:
     """Static buffers of one (batch size, resolution, heatmaps wanted) and, once
     captured, the graph that maps its inputs to its outputs."""
 
-    def __init__(self, M, N, K, R, flip, want_hm, dev):
+    def __init__(self, M, N, K, R, flip, want_hm, dev, refine=False):
         H = W = R // 4
         f32 = dict(device=dev, dtype=torch.float32)
         self.N, self.H, self.W = N, H, W
@@ -53,6 +59,12 @@ class _Slot:
         self.scores = torch.zeros((M, N, K), **f32)
         self.mean = torch.zeros((N, K, 2), **f32)
         self.heatmaps = torch.zeros((M, N, K, H, W), **f32) if want_hm else None
+        self.refine = refine
+        if refine:                                  # the sub-pixel decode's outputs (Predictor(refine=...))
+            self.raw_sub = torch.zeros((M, N, K, 2), **f32)
+            self.preds_sub = torch.zeros((M, N, K, 2), **f32)
+            self.rule = torch.zeros((M, N, K), **f32)
+            self.mean_sub = torch.zeros((N, K, 2), **f32)
         self.graph = None
 
     def release(self):
@@ -66,8 +78,8 @@ class _PseudoSlot(_Slot):
     (the ensemble kernel reads them in place), the ensemble outputs and the threshold.
     One slot serves calls with and without return_heatmaps."""
 
-    def __init__(self, M, N, K, R, flip, dev):
-        super().__init__(M, N, K, R, flip, True, dev)
+    def __init__(self, M, N, K, R, flip, dev, refine=False):
+        super().__init__(M, N, K, R, flip, True, dev, refine)
         f32 = dict(device=dev, dtype=torch.float32)
         self.thr = torch.zeros(1, **f32)
         self.ens_raw = torch.zeros((N, K, 2), **f32)
@@ -77,15 +89,31 @@ class _PseudoSlot(_Slot):
         self.select = torch.zeros((M, N, K), **f32)
         self.spread = torch.zeros((N, K), **f32)
         self.mean_hm = torch.zeros((N, K, self.H, self.W), **f32)
+        if refine:
+            self.ens_raw_sub = torch.zeros((N, K, 2), **f32)
+            self.ens_preds_sub = torch.zeros((N, K, 2), **f32)
+            self.ens_rule = torch.zeros((N, K), **f32)
 
 
+DEFAULT_BLUR_SIGMA = 1.0
 RULES = ("unanimous", "ensemble")
+REFINES = ("none", "quarter", "taylor")
 
 
 def check_rule(rule):
     if rule not in RULES:
         raise ValueError("ubpl_amd: rule is one of %s, got %r" % (", ".join(RULES), rule))
     return rule
+
+
+def check_refine(refine, blur_sigma):
+    """The refine / blur_sigma arguments -> (refine, the host taps table or None for "none").
+    The blur belongs to "taylor"; "quarter" reads unblurred values."""
+    if refine not in REFINES:
+        raise ValueError("ubpl_amd: refine is one of %s, got %r" % (", ".join(REFINES), refine))
+    if refine == "none":
+        return refine, None
+    return refine, Kn.blur_taps(blur_sigma if refine == "taylor" else 0.0)
 
 
 def assemble_kps(ens_preds, selected):
@@ -95,7 +123,8 @@ def assemble_kps(ens_preds, selected):
 
 
 class Predictor:
-    """Predictor(models, flip_test=False, flip_pairs=None, max_batch=32, max_graphs=4, graph=None)
+    """Predictor(models, flip_test=False, flip_pairs=None, max_batch=32, max_graphs=4, graph=None,
+              refine="none", blur_sigma=DEFAULT_BLUR_SIGMA)
 
     models      one StackedHourglass or a list (the teachers), same k, one device;
     flip_test   average each heatmap with the flipped-back heatmap of the mirrored image;
@@ -104,7 +133,14 @@ class Predictor:
                 utils/process.py:239-242);
     max_batch   larger inputs run in chunks of this size;
     max_graphs  captured graphs kept (one per exact batch size, least recently used out);
-    graph       None: on unless UBPL_PREDICT_GRAPH=0; False: the same path eagerly.
+    graph       None: on unless UBPL_PREDICT_GRAPH=0; False: the same path eagerly;
+    refine      "none": integer peaks only, no further launch or result key.  "quarter" /
+                "taylor": one ubpl_refine_peaks launch after each network's decode (inside the
+                graph) adds sub-pixel coordinates under the keys raw_sub, preds_sub,
+                preds_mean_sub and refine_rule (pseudo_label: also ens_raw_sub, ens_preds_sub,
+                ens_refine_rule, kps_sub); raw, preds and preds_mean keep their integer meaning;
+    blur_sigma  "taylor" only: sigma in heatmap cells of the Gaussian blur of the window around
+                the peak (0: none; at most 2.0).
 
     Snapshot semantics: construction and refresh() copy the networks' parameters and
     running statistics into private frozen weight sets; training steps, EMA updates or
@@ -112,7 +148,10 @@ class Predictor:
     networks' training flag, statistics, counters, parameters and own weight buffers are
     never touched."""
 
-    def __init__(self, models, flip_test=False, flip_pairs=None, max_batch=32, max_graphs=4, graph=None):
+    def __init__(self, models, flip_test=False, flip_pairs=None, max_batch=32, max_graphs=4, graph=None,
+                 refine="none", blur_sigma=DEFAULT_BLUR_SIGMA):
+        self.refine, taps = check_refine(refine, blur_sigma)
+        self.blur_sigma = float(blur_sigma) if refine == "taylor" else None
         _lib.require_gpu()
         from .hourglass import StackedHourglass
         self.models = [models] if isinstance(models, StackedHourglass) else list(models)
@@ -128,6 +167,7 @@ class Predictor:
         self.perm = None
         if flip_pairs:
             self.perm = Kn.flip_perm(self.k, flip_pairs).to(self.device)
+        self.taps = None if taps is None else taps.to(self.device)
         self.max_batch, self.max_graphs = int(max_batch), int(max_graphs)
         self.use_graph = os.environ.get("UBPL_PREDICT_GRAPH", "1") != "0" if graph is None else bool(graph)
         self._slots = OrderedDict()
@@ -175,7 +215,12 @@ class Predictor:
             Kn.decode_heatmaps_flip(hm, hm_flip, sb, N, K, H, W, self.perm, s.tinv,
                                     out=(s.raw[mi], s.preds[mi], s.scores[mi],
                                          s.heatmaps[mi] if s.heatmaps is not None else None))
+            if s.refine:
+                Kn.refine_peaks(hm, hm_flip, sb, N, K, H, W, self.perm, s.raw[mi], self.refine, self.taps, s.tinv,
+                                out=(s.raw_sub[mi], s.preds_sub[mi], s.rule[mi]))
         s.mean.copy_(torch.stack(list(s.preds), -1).mean(-1))       # projects/MT_UBPL.py:387
+        if s.refine:
+            s.mean_sub.copy_(torch.stack(list(s.preds_sub), -1).mean(-1))
 
     def _slot(self, N, R, want_hm, pseudo=False):
         # (pseudo_label's slots carry a key of their own: predict's graphs and buffers stay its own)
@@ -190,7 +235,8 @@ class Predictor:
             del old
             torch.cuda.empty_cache()
         a = (len(self.models), N, self.k, R, self.flip_test)
-        s = self._slots[key] = _PseudoSlot(*a, self.device) if pseudo else _Slot(*a, want_hm, self.device)
+        on = self.refine != "none"
+        s = self._slots[key] = _PseudoSlot(*a, self.device, on) if pseudo else _Slot(*a, want_hm, self.device, on)
         return s, True
 
     def _launch(self, s, new, run):
@@ -209,6 +255,11 @@ class Predictor:
             s.graph = g
         s.graph.replay()
 
+    def _sub_keys(self, s, have):
+        """The sub-pixel entries of a predict / pseudo_label result (refine on)."""
+        return {"raw_sub": s.raw_sub.clone(), "preds_sub": s.preds_sub.clone() if have else None,
+                "preds_mean_sub": s.mean_sub.clone() if have else None, "refine_rule": s.rule.clone()}
+
     def _predict_chunk(self, imgs, tinv, want_hm):
         N, R = imgs.shape[0], imgs.shape[2]
         s, new = self._slot(N, R, want_hm)
@@ -219,6 +270,8 @@ class Predictor:
         out = {"raw": s.raw.clone(), "scores": s.scores.clone(),
                "preds": s.preds.clone() if tinv is not None else None,
                "preds_mean": s.mean.clone() if tinv is not None else None}
+        if s.refine:
+            out.update(self._sub_keys(s, tinv is not None))
         if want_hm:
             out["heatmaps"] = s.heatmaps.clone()
         return out
@@ -255,7 +308,8 @@ class Predictor:
                 outs.append(self._predict_chunk(imgs[a:b], None if tinv is None else tinv[a:b], bool(return_heatmaps)))
         if len(outs) == 1:
             return outs[0]
-        return {k: None if outs[0][k] is None else torch.cat([o[k] for o in outs], 0 if k == "preds_mean" else 1)
+        per_sample = ("preds_mean", "preds_mean_sub")
+        return {k: None if outs[0][k] is None else torch.cat([o[k] for o in outs], 0 if k in per_sample else 1)
                 for k in outs[0]}
 
     # -- ensemble pseudo-labels --------------------------------------------
@@ -270,6 +324,9 @@ class Predictor:
                                 s.mean_hm))
         d = s.raw - s.ens_raw
         s.spread.copy_((d * d).sum(-1).sqrt().amax(0))
+        if s.refine:                                                # the ensemble peak, on T itself
+            Kn.refine_peaks(s.mean_hm, None, K * H * W, N, K, H, W, None, s.ens_raw, self.refine, self.taps, s.tinv,
+                            out=(s.ens_raw_sub, s.ens_preds_sub, s.ens_rule))
 
     def _pseudo_chunk(self, imgs, tinv, thr, rule, want_hm):
         N, R = imgs.shape[0], imgs.shape[2]
@@ -289,12 +346,18 @@ class Predictor:
                "ens_score": s.ens_score.clone(), "member_select": select, "disagree": s.disagree.clone(),
                "selected": selected, "spread": s.spread.clone(),
                "kps": assemble_kps(s.ens_preds, selected) if have else None}
+        if s.refine:
+            out.update(self._sub_keys(s, have))
+            out.update({"ens_raw_sub": s.ens_raw_sub.clone(), "ens_preds_sub": s.ens_preds_sub.clone() if have else None,
+                        "ens_refine_rule": s.ens_rule.clone(),
+                        "kps_sub": assemble_kps(s.ens_preds_sub, selected) if have else None})
         if want_hm:
             out["heatmaps"] = s.heatmaps.clone()
             out["mean_heatmap"] = s.mean_hm.clone()
         return out
 
-    _PER_MEMBER = ("raw", "scores", "preds", "member_select", "disagree", "heatmaps")
+    _PER_MEMBER = ("raw", "scores", "preds", "member_select", "disagree", "heatmaps", "raw_sub", "preds_sub",
+                   "refine_rule")
 
     def pseudo_label(self, imgs, center=None, scale=None, thr=0.95, rule="unanimous", return_heatmaps=False,
                      out_res=None):
@@ -313,6 +376,9 @@ class Predictor:
           spread [N,K]                       max over m of |raw[m] - ens_raw|, heatmap pixels;
           kps [N,K,3]                        (ens_preds x, y, selected as 0/1), the meta["kpsMap"]
                                              layout (None without center / scale);
+        with refine on, predict's sub-pixel keys and ens_raw_sub [N,K,2], ens_preds_sub [N,K,2],
+        ens_refine_rule [N,K] (the refinement of the ensemble peak on T) and kps_sub [N,K,3]
+        (ens_preds_sub x, y, selected); spread stays on the integer peaks;
         with return_heatmaps, heatmaps [M,N,K,H,W] and mean_heatmap [N,K,H,W] (T).
         thr defaults to the reference's pseudoScoreThr; one captured graph serves every thr."""
         check_rule(rule)
@@ -335,14 +401,16 @@ class Predictor:
         """pseudo_label over a loader of (imgMap, _, meta) batches with meta["center"] /
         meta["scale"] (the shape validate takes; args.outRes, when given, is the resolution of
         the inverse transform).  -> a host dict of plain lists, sample-major: predsArraies
-        (the reference's key, projects/MT_UBPL.py:120: [x, y] per joint from ens_preds),
+        (the reference's key, projects/MT_UBPL.py:120: [x, y] per joint from ens_preds; with
+        refine on from ens_preds_sub, and the dict records "refine" and "blur_sigma"),
         selected, ens_score, spread [N][K], disagree [N][M][K], thr, rule and
         selected_fraction [K].  Single process only, as validate."""
         from . import dist as D
         if D.is_dist():
             raise NotImplementedError("ubpl_amd: Predictor.label_pool runs in one process")
         check_rule(rule)
-        keys = ("ens_preds", "selected", "ens_score", "spread", "disagree")
+        on = self.refine != "none"
+        keys = ("ens_preds_sub" if on else "ens_preds", "selected", "ens_score", "spread", "disagree")
         cols = {k: [] for k in keys}
         for imgMap, _, meta in loader:
             out = self.pseudo_label(imgMap.float(), meta["center"], meta["scale"], thr=thr, rule=rule,
@@ -352,16 +420,19 @@ class Predictor:
                 cols[k].append(out[k].cpu())
         cat = {k: torch.cat(v) if v else torch.zeros(0) for k, v in cols.items()}
         sel = cat["selected"]
-        return {"predsArraies": cat["ens_preds"].tolist(), "selected": sel.tolist(),
-                "ens_score": cat["ens_score"].tolist(), "spread": cat["spread"].tolist(),
-                "disagree": cat["disagree"].tolist(), "thr": float(thr), "rule": rule,
-                "selected_fraction": sel.float().mean(0).tolist() if sel.numel() else []}
+        d = {"predsArraies": cat[keys[0]].tolist(), "selected": sel.tolist(),
+             "ens_score": cat["ens_score"].tolist(), "spread": cat["spread"].tolist(),
+             "disagree": cat["disagree"].tolist(), "thr": float(thr), "rule": rule,
+             "selected_fraction": sel.float().mean(0).tolist() if sel.numel() else []}
+        if on:
+            d.update({"refine": self.refine, "blur_sigma": self.blur_sigma})
+        return d
 
     def validate(self, loader, args):
         """train.validate(loader, models, args) from the frozen snapshot: the same triple
         (predsArray, accs_records, errs_records), folded by the same code.  Single process
         only: under torch.distributed this raises NotImplementedError (train.validate shards
-        and gathers the batches)."""
+        and gathers the batches).  With refine on, the sub-pixel predictions are scored."""
         from . import dist as D
         from . import train as T
         if D.is_dist():
@@ -370,6 +441,7 @@ class Predictor:
         rows = []
         for imgMap, _, meta in loader:
             out = self.predict(imgMap.float(), meta["center"], meta["scale"], out_res=args.outRes)
-            pm = list(out["preds"]) + [out["preds_mean"]]
+            sub = "_sub" if self.refine != "none" else ""
+            pm = list(out["preds" + sub]) + [out["preds_mean" + sub]]
             rows.append(T.valid_batch_row(pm, meta, self.device, args))
         return T.fold_valid_rows(rows, len(self.models) + 1)

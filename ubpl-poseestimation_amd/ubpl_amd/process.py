@@ -65,16 +65,26 @@ class ProcessUtils:
         return hms, news
 
     @classmethod
-    def kps_fromHeatmap(cls, heatmap, cenMap, scale, res, mode="batch"):
+    def kps_fromHeatmap(cls, heatmap, cenMap, scale, res, mode="batch", refine="none", blur_sigma=None):
+        """refine "quarter" / "taylor" (beyond the reference's signature): the sub-pixel
+        coordinates of ubpl_refine_peaks, untruncated, in place of the integer ones;
+        blur_sigma: Taylor's blur (None: Predictor's default)."""
         if mode == "single":
             p, _ = cls.kps_fromHeatmap(heatmap.unsqueeze(0), torch.as_tensor(cenMap).unsqueeze(0),
-                                       torch.as_tensor(scale).reshape(1), res)
+                                       torch.as_tensor(scale).reshape(1), res, refine=refine, blur_sigma=blur_sigma)
             return p[0]
+        taps = None
+        if refine != "none":
+            from .predict import DEFAULT_BLUR_SIGMA, check_refine
+            refine, taps = check_refine(refine, DEFAULT_BLUR_SIGMA if blur_sigma is None else blur_sigma)
         _lib.require_gpu()
         dev = heatmap.device
         hm = heatmap.detach().to("cuda", torch.float32).contiguous()
         tinv = inverse_transforms(cenMap, scale, res).to("cuda")
-        _, preds, scores = Kn.decode_heatmaps(hm, tinv)
+        raw, preds, scores = Kn.decode_heatmaps(hm, tinv)
+        if taps is not None:
+            N, K, H, W = hm.shape
+            _, preds, _ = Kn.refine_peaks(hm, None, K * H * W, N, K, H, W, None, raw, refine, taps.to("cuda"), tinv)
         return preds.to(dev), scores.to(dev)
 
     @classmethod
