@@ -162,6 +162,48 @@ int ubpl_ensemble_pseudo(const float* hm, int64_t sm, int64_t sb, int M, int N, 
 int ubpl_refine_peaks(const float* hm, const float* hm_flip, int64_t sb, int N, int K, int H, int W,
                       const int* perm, const float* raw, int mode, const float* taps, int radius,
                       const double* tinv, float* raw_sub, float* preds_sub, float* how, void* stream);
+/* Multi-view test-time augmentation.  The reference computes a warp matrix per
+ * augmented view (utils/augment.py:158-164 affine_getWarpmat) and can warp a
+ * view's heatmaps back (affine_back2, :36-47: F.affine_grid / F.grid_sample
+ * with align_corners=True, then the flip-back), used by a debug drawing only
+ * (projects/MT_UBPL.py:186-205).  Both entries take PIXEL-space 2x3 matrices,
+ * output pixel -> source pixel, row-major (m0 .. m5), built on the host in f64
+ * and rounded to f32, the mirror folded in (kernels.view_matrices;
+ * kernels.affine_theta_to_pixels converts affine_grid's normalised convention).
+ * The one sampling rule of a plane p [H,W] at output pixel (x, y) under m, every
+ * product, sum and quotient its own f32 rounding (no FMA):
+ *   sx = (m0*x + m1*y) + m2,  sy = (m3*x + m4*y) + m5;
+ *   outside unless -1 < sx < W and -1 < sy < H (a NaN or an infinity is
+ *   outside; tested before any float -> int conversion): s = 0, cov = 0;
+ *   x0 = floorf(sx), ax = sx - x0, bx = 1 - ax, y0, ay, by likewise; the taps
+ *   v00 = p[y0,x0], v01 = p[y0,x0+1], v10 = p[y0+1,x0], v11 = p[y0+1,x0+1],
+ *   each 0 where its index is outside the plane;
+ *   top = v00*bx + v01*ax, bot = v10*bx + v11*ax, s = top*by + bot*ay;
+ *   cov = the same formula over the taps' in-bounds indicators (1 / 0);
+ *   a matrix that is exactly (1,0,0,0,1,0): s = p[y,x], cov = 1, no arithmetic.
+ * ubpl_warp_views: src [N,C,H,W], mat [V,6] -> out [V,N,C,H,W], out[v] = s of
+ * every plane under mat[v] (an identity view is a copy). */
+/*@ src:f32[(int64_t)N*C*H*W] mat:f32[V*6] out:f32[(int64_t)V*N*C*H*W] */
+int ubpl_warp_views(const float* src, int N, int C, int H, int W, const float* mat, int V, float* out,
+                    void* stream);
+/* ubpl_decode_heatmaps_views: view v's map (n, k) starts at hm + v*sv + n*sb +
+ * k'*H*W (strides in floats: the last stacks of a view-major [V*N,S,K,H,W]
+ * output in place with sv = N*sb), k' = perm[k] where swap[v] != 0, else k
+ * (swap int32 [V], null = none; perm int32 [K], null = identity, an entry
+ * outside [0, K) falls back to k).  1 <= V <= 16 (hipErrorInvalidValue
+ * otherwise).  Per output pixel, views in ascending v: num = s_0, den = cov_0,
+ * then num = num + s_v, den = den + cov_v (sequential f32 sums); merged = num /
+ * den (one IEEE f32 division) where den > 0, else 0 — a pixel a rotated or
+ * zoomed view does not cover is averaged over the views that cover it.  So V =
+ * 1 with the identity matrix is the plain strided decode (NaN and inf rules
+ * included), and identity + mirror is ubpl_decode_heatmaps_flip's (a + b) *
+ * 0.5f.  merged [N,K,H,W] (nullable); raw, preds, scores, tinv as in
+ * ubpl_decode_heatmaps_flip, decoded from the same registers.  No atomics, no
+ * cross-pixel sums: repeated launches give equal bits. */
+/*@ hm:f32[(V-1)*sv+(N-1)*sb+(int64_t)K*H*W] mat:f32[V*6] swap:i32[V] perm:i32[K] tinv:f64[N*6] merged:f32[(int64_t)N*K*H*W] raw:f32[N*K*2] preds:f32[N*K*2] scores:f32[N*K] */
+int ubpl_decode_heatmaps_views(const float* hm, int64_t sv, int64_t sb, int V, int N, int K, int H, int W,
+                               const float* mat, const int* swap, const int* perm, const double* tinv,
+                               float* merged, float* raw, float* preds, float* scores, void* stream);
 /* EvaluationUtils.acc_pck (utils/evaluation.py:91-139).  errs/accs [K+1];
  * hits/valid [K] int32 (nullable) for cross-rank aggregation. */
 /*@ preds:f32[N*K*2] gts:f32[N*K*3] errs:f32[K+1] accs:f32[K+1] hits:i32[K] valid:i32[K] */

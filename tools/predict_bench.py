@@ -40,6 +40,16 @@ teacher that differ in the option alone:
 
 Same warm-up, rounds and report; the integer outputs of the three must agree bit for bit
 before anything is timed.
+
+--mode tta times multi-view test-time augmentation, on Predictors of the same teacher that
+differ in tta / flip_test alone:
+
+  (none)  Predictor.predict(x, center, scale) with tta=None — the comparison;
+  (v1)    tta=[(0, 1)]: one view through ubpl_decode_heatmaps_views;
+  (v3)    three zooms;  (v5) three zooms + two rotations;  (v10) those five with flip_test.
+
+Same warm-up, rounds and report; v1 and none must agree bit for bit before anything is timed.
+A Predictor with tta keeps its forward batch within 2 max_batch images, so larger B run in chunks.
 """
 import argparse
 import json
@@ -134,6 +144,46 @@ def refine_main(a):
     print(line)
 
 
+TTA_ZOOMS = [(0, 1), (0, 0.85), (0, 1.15)]
+TTA_ROTATIONS = [(15, 1), (-15, 1)]
+
+
+def tta_main(a):
+    from ubpl_amd import Predictor, _lib, kernels as Kn
+    _lib.require_gpu()
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    gen = torch.Generator().manual_seed(1)
+    model = teacher(a, 0, gen, dev)
+    kw = refine_kw(a)
+    P = {"none": Predictor(model, **kw), "v1": Predictor(model, tta=[(0, 1)], **kw),
+         "v3": Predictor(model, tta=TTA_ZOOMS, **kw), "v5": Predictor(model, tta=TTA_ZOOMS + TTA_ROTATIONS, **kw),
+         "v10": Predictor(model, tta=TTA_ZOOMS + TTA_ROTATIONS, flip_test=True, **kw)}
+    rows = []
+    for B in [int(b) for b in a.batches.split(",")]:
+        x = (torch.rand(B, 3, a.res, a.res, generator=gen) - 0.5).to(dev)
+        center = torch.full((B, 2), a.res / 2.0)
+        scale = torch.full((B,), a.res / 200.0)
+        outs = {n: p.predict(x, center, scale) for n, p in P.items()}
+        if not all(torch.equal(outs["v1"][k], outs["none"][k]) for k in outs["none"]):
+            raise SystemExit("predict_bench: tta=[(0, 1)] and tta=None disagree at B=%d" % B)
+        row = {"B": B, "chunk": {n: min(B, p.max_batch) for n, p in P.items()}}
+        row.update(measure({n: (lambda p=p: p.predict(x, center, scale)) for n, p in P.items()}, a))
+        for n, p in P.items():
+            if n != "none":
+                row[n + "_over_none"] = round(row[n + "_ms"] / row["none_ms"], 3)
+        rows.append(row)
+    out = {"tool": "predict_bench", "mode": "tta", "model": "HG%d" % a.stacks, "k": a.k, "res": a.res,
+           "views": {"v1": 1, "v3": 3, "v5": 5, "v10": 10}, "zooms": TTA_ZOOMS, "rotations": TTA_ROTATIONS,
+           "refine": a.refine, "precision": Kn.conv_precision_name(), "repeats": a.repeats,
+           "device": torch.cuda.get_device_name(0), "rows": rows}
+    line = json.dumps(out)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
 def pseudo_main(a):
     from ubpl_amd import Predictor, _lib, kernels as Kn
     from ubpl_amd.hourglass import StackedHourglass
@@ -199,7 +249,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--window", type=float, default=0.25, help="seconds of work per variant per round")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--mode", default="predict", choices=["predict", "pseudo", "refine"])
+    ap.add_argument("--mode", default="predict", choices=["predict", "pseudo", "refine", "tta"])
     ap.add_argument("--refine", default="none", choices=["none", "quarter", "taylor"])
     ap.add_argument("--blur-sigma", type=float, default=None, help="taylor's blur (default: the Predictor's)")
     ap.add_argument("--thr", type=float, default=0.95, help="--mode pseudo: the score threshold (<= 0: each batch's median ensemble score)")
@@ -208,6 +258,8 @@ def main():
         return pseudo_main(a)
     if a.mode == "refine":
         return refine_main(a)
+    if a.mode == "tta":
+        return tta_main(a)
 
     from ubpl_amd import Predictor, _lib, kernels as Kn
     from ubpl_amd.hourglass import StackedHourglass

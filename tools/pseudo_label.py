@@ -10,7 +10,7 @@ pck_thr of the truth, for the selected joints and for all of them.
     python tools/pseudo_label.py [--ckpt ckpts/checkpoint_best.pth.tar] [--model HG2]
                                  [--thr 0.95] [--rule unanimous|ensemble] [--flip] [--out FILE]
                                  [--refine none|quarter|taylor|all] [--blur-sigma S]
-                                 [--train-epochs E] [--record FILE]
+                                 [--train-epochs E] [--record FILE] [--tta rows|A:Z,A:Z,...]
 
 --refine / --blur-sigma: the Predictor's sub-pixel decode (predsArraies then holds the
 sub-pixel coordinates).  --refine all labels the split once per variant — none, quarter,
@@ -18,6 +18,11 @@ taylor at blur sigma 0, 1 and 2 — with the same weights, and --record writes, 
 PCK@pck_thr of the ensemble peak, of the teachers' mean (Predictor.validate) and the mean
 pixel error over the valid joints.  --train-epochs E: without --ckpt, train the teachers
 first by E epochs of tools/mouse_pck.py's experiment (once, shared by every variant).
+
+--tta: the Predictor's test-time augmentation, as angle_deg:zoom pairs whose first is 0:1
+(with --flip every view also mirrored).  --tta rows labels the split once per row of views —
+none; flip; three zooms; three zooms + two rotations; those five with flip — for every refine
+variant asked for (--refine takes a comma-separated list too), with the same weights.
 
 Reads tests/golden/mouse_100_500_0.3/ (tools/pack_mouse.py).  Untrained networks select
 next to nothing at the default threshold; that is the expected output without --ckpt.
@@ -43,6 +48,23 @@ def within_pck(preds, gts, ref, thr):
     return (dist / norm < thr) & valid, valid
 
 
+TTA_ZOOMS = [(0.0, 1.0), (0.0, 0.85), (0.0, 1.15)]
+TTA_ROTATIONS = [(15.0, 1.0), (-15.0, 1.0)]
+TTA_ROWS = [("none", None, False), ("flip", None, True), ("3 zooms", TTA_ZOOMS, False),
+            ("3 zooms + 2 rotations", TTA_ZOOMS + TTA_ROTATIONS, False),
+            ("3 zooms + 2 rotations, flip", TTA_ZOOMS + TTA_ROTATIONS, True)]
+
+
+def tta_rows(spec, flip):
+    """--tta / --flip -> [(row name, views or None, flip_test)]."""
+    if spec is None:
+        return [("flip" if flip else "none", None, flip)]
+    if spec == "rows":
+        return TTA_ROWS
+    views = [tuple(float(v) for v in item.split(":")) for item in spec.split(",")]
+    return [(spec + (", flip" if flip else ""), views, flip)]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ckpt", default=None)
@@ -54,7 +76,8 @@ def main():
     ap.add_argument("--inferBS", type=int, default=32)
     ap.add_argument("--limit", type=int, default=0, help="label only the first batches up to this many images")
     ap.add_argument("--out", default=os.path.join(ROOT, "build", "pseudo_labels.json"))
-    ap.add_argument("--refine", default="none", choices=["none", "quarter", "taylor", "all"])
+    ap.add_argument("--refine", default="none", help="none, quarter, taylor, a comma-separated list of them, or all")
+    ap.add_argument("--tta", default=None, help="angle:zoom,... (first 0:1), or rows")
     ap.add_argument("--blur-sigma", type=float, default=None, help="taylor's blur (default: the Predictor's)")
     ap.add_argument("--train-epochs", type=int, default=0, help="without --ckpt: train the teachers this long first")
     ap.add_argument("--record", default=None, help="write the per-variant accuracy figures here")
@@ -88,17 +111,19 @@ def main():
         loader = loader[:max(1, a.limit // a.inferBS)]
     gts = torch.cat([m["kpsMap"] for _, _, m in loader])
     sigma = DEFAULT_BLUR_SIGMA if a.blur_sigma is None else a.blur_sigma
-    variants = [(a.refine, sigma)] if a.refine != "all" else \
+    variants = [(r, sigma) for r in a.refine.split(",")] if a.refine != "all" else \
         [("none", sigma), ("quarter", sigma), ("taylor", 0.0), ("taylor", 1.0), ("taylor", 2.0)]
+    rows_of_views = tta_rows(a.tta, a.flip)
     vargs = types.SimpleNamespace(outRes=data.outRes, pck_ref=data.pck_ref, pck_thr=data.pck_thr)
     rows = []
-    for refine, sg in variants:
-        P = Predictor(teachers, flip_test=a.flip, max_batch=a.inferBS, refine=refine, blur_sigma=sg)
+    for refine, sg, (row_name, views, flip) in [(r, g, t) for r, g in variants for t in rows_of_views]:
+        P = Predictor(teachers, flip_test=flip, max_batch=a.inferBS, refine=refine, blur_sigma=sg, tta=views)
         d = P.label_pool(loader, types.SimpleNamespace(outRes=data.outRes), thr=a.thr, rule=a.rule)
-        d["source"] = {"ckpt": a.ckpt, "model": a.model, "teachers": a.teachers, "flip_test": a.flip,
+        d["source"] = {"ckpt": a.ckpt, "model": a.model, "teachers": a.teachers, "flip_test": flip,
                        "split": "Mouse_100_500_0.3 valid", "images": len(d["predsArraies"]), "trained": trained}
-        out = a.out if len(variants) == 1 else "%s.%s%s.json" % (
-            os.path.splitext(a.out)[0], refine, "_s%g" % sg if refine == "taylor" else "")
+        out = a.out if len(variants) * len(rows_of_views) == 1 else "%s.%s%s%s.json" % (
+            os.path.splitext(a.out)[0], refine, "_s%g" % sg if refine == "taylor" else "",
+            "" if len(rows_of_views) == 1 else ".v%d" % (P.views or (2 if flip else 1)))
         checkpoint.save_pseudo_data(d, out)
         preds = torch.tensor(d["predsArraies"])
         sel = torch.tensor(d["selected"])
@@ -107,6 +132,8 @@ def main():
         _, accs, _ = P.validate(loader, vargs)
         P.release()
         rows.append({"out": out, "refine": refine, "blur_sigma": sg if refine == "taylor" else None,
+                     "views": row_name, "tta": views, "flip_test": flip,
+                     "forward_passes_per_image": P.views or (2 if flip else 1),
                      "images": len(preds), "thr": a.thr, "rule": a.rule,
                      "selected_fraction": round(float(sel.float().mean()), 4),
                      "selected_fraction_per_joint": [round(v, 4) for v in d["selected_fraction"]],

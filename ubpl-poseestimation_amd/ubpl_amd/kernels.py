@@ -302,6 +302,160 @@ def refine_peaks(hm, hm_flip, sb, N, K, H, W, perm, raw, mode, taps, tinv=None, 
     return raw_sub, preds_sub, how
 
 
+# ---- multi-view test-time augmentation (csrc/decode_warp.hip; the convention: DESIGN.md §4)
+MAX_VIEWS = 16
+F64 = torch.float64
+
+
+def _mat6(m):
+    return torch.as_tensor(m, dtype=F64).reshape(-1, 6)
+
+
+def compose_pixels(a, b):
+    """Pixel matrices [...,6] (output pixel -> source pixel) -> a o b: b first, then a, in float64."""
+    a, b = _mat6(a), _mat6(b)
+    out = torch.empty(torch.broadcast_shapes(a.shape, b.shape), dtype=F64)
+    for r in (0, 3):
+        out[:, r + 0] = a[:, r] * b[:, 0] + a[:, r + 1] * b[:, 3]
+        out[:, r + 1] = a[:, r] * b[:, 1] + a[:, r + 1] * b[:, 4]
+        out[:, r + 2] = a[:, r] * b[:, 2] + a[:, r + 1] * b[:, 5] + a[:, r + 2]
+    return out
+
+
+def mirror_pixels(W):
+    """m(x, y) = (W - 1 - x, y) as a pixel matrix [1,6] (float64)."""
+    return torch.tensor([[-1.0, 0.0, W - 1.0, 0.0, 1.0, 0.0]], dtype=F64)
+
+
+def affine_theta_to_pixels(theta, H, W):
+    """theta [V,2,3] (or [2,3]) of F.affine_grid(..., align_corners=True) on [H,W] planes — the
+    reference's affine_back2 convention, utils/augment.py:36-47: normalised output position ->
+    normalised source position, -1 and 1 the centres of the first and last pixel — -> the pixel
+    matrices [V,6] float64 (output pixel -> source pixel) that sample the same positions."""
+    if H < 2 or W < 2:
+        raise ValueError("ubpl_amd: align_corners=True normalises over H - 1 and W - 1; %dx%d has none" % (H, W))
+    t = torch.as_tensor(theta, dtype=F64).reshape(-1, 2, 3)
+    hx, hy = (W - 1) / 2.0, (H - 1) / 2.0
+    m = torch.empty((t.shape[0], 6), dtype=F64)
+    m[:, 0] = t[:, 0, 0]
+    m[:, 1] = t[:, 0, 1] * (hx / hy)
+    m[:, 2] = hx * (t[:, 0, 2] + 1.0 - t[:, 0, 0] - t[:, 0, 1])
+    m[:, 3] = t[:, 1, 0] * (hy / hx)
+    m[:, 4] = t[:, 1, 1]
+    m[:, 5] = hy * (t[:, 1, 2] + 1.0 - t[:, 1, 0] - t[:, 1, 1])
+    return m
+
+
+def affine_pixels_to_theta(mat, H, W):
+    """The inverse of affine_theta_to_pixels: pixel matrices [V,6] -> theta [V,2,3] float64."""
+    if H < 2 or W < 2:
+        raise ValueError("ubpl_amd: align_corners=True normalises over H - 1 and W - 1; %dx%d has none" % (H, W))
+    m = _mat6(mat)
+    hx, hy = (W - 1) / 2.0, (H - 1) / 2.0
+    t = torch.empty((m.shape[0], 2, 3), dtype=F64)
+    t[:, 0, 0] = m[:, 0]
+    t[:, 0, 1] = m[:, 1] * (hy / hx)
+    t[:, 0, 2] = m[:, 2] / hx - 1.0 + t[:, 0, 0] + t[:, 0, 1]
+    t[:, 1, 0] = m[:, 3] * (hx / hy)
+    t[:, 1, 1] = m[:, 4]
+    t[:, 1, 2] = m[:, 5] / hy - 1.0 + t[:, 1, 0] + t[:, 1, 1]
+    return t
+
+
+def _about_centre(a, S):
+    """q -> c + a (q - c), c = ((S-1)/2, (S-1)/2), a a 2x2 nested list -> one matrix row [6]."""
+    c = (S - 1) / 2.0
+    return [a[0][0], a[0][1], c - a[0][0] * c - a[0][1] * c, a[1][0], a[1][1], c - a[1][0] * c - a[1][1] * c]
+
+
+def view_matrices(views, flip, R, H):
+    """The matrices of test-time-augmentation views on square planes ("Multi-view
+    decode").  views: [(angle_deg, zoom), ...]; A = R(angle) / zoom, R(a) = [[cos a, -sin a],
+    [sin a, cos a]], y down, so zoom > 1 magnifies.  The view image is view(q) = img(c + A (q - c));
+    the original frame's heatmap at p samples the view's at q = c_h + A^-1 (p - c_h).  flip: every
+    view once more mirrored, after the plain ones — view_f(q) = view(m(q)), its heatmap sampled at
+    m(q), m(x, y) = (S - 1 - x, y) — with swap = 1 (the joint permutation is not geometry).
+    -> host (img_mat [V,6] on [R,R] planes, hm_mat [V,6] on [H,H] planes, both output pixel ->
+    source pixel, float64 rounded to float32; swap [V] int32)."""
+    img, hm = [], []
+    for angle, zoom in views:
+        a = math.radians(float(angle))
+        co, si, z = math.cos(a), math.sin(a), float(zoom)
+        img.append(_about_centre([[co / z, -si / z], [si / z, co / z]], R))
+        hm.append(_about_centre([[co * z, si * z], [-si * z, co * z]], H))
+    img, hm = _mat6(img), _mat6(hm)
+    swap = [0] * len(img)
+    if flip:
+        # view_f(q) = img(M m(q)): M o m on the image; the heatmap is read at m(q(p)): m o M
+        img = torch.cat([img, compose_pixels(img, mirror_pixels(R))])
+        hm = torch.cat([hm, compose_pixels(mirror_pixels(H), hm)])
+        swap = swap + [1] * len(swap)
+    return img.to(F32), hm.to(F32), torch.tensor(swap, dtype=torch.int32)
+
+
+def warp_views(src, mat, out=None):
+    """Views of a batch (ubpl_warp_views): src [N,C,H,W], mat device float32 [V,6] pixel matrices
+    (output pixel -> source pixel) -> out [V,N,C,H,W] (or any contiguous tensor of that many
+    floats, e.g. rows of a [V*N,C,H,W] batch), bilinear, zero outside; an identity view copies."""
+    _chk(src, "src")
+    _chk(mat, "mat")
+    if src.dim() != 4 or mat.dim() != 2 or mat.shape[1] != 6:
+        raise ValueError("ubpl_amd: warp_views takes src [N,C,H,W] and mat [V,6]")
+    N, C, H, W = src.shape
+    V = mat.shape[0]
+    if out is None:
+        out = torch.empty((V, N, C, H, W), device=src.device, dtype=F32)
+    _chk(out, "out")
+    if out.numel() != V * src.numel():
+        raise ValueError("ubpl_amd: out holds %d floats, %d views of %d need %d"
+                         % (out.numel(), V, src.numel(), V * src.numel()))
+    if V * src.numel():
+        lo, hi = src.data_ptr(), src.data_ptr() + src.numel() * 4
+        if out.data_ptr() < hi and lo < out.data_ptr() + out.numel() * 4:
+            raise ValueError("ubpl_amd: warp_views writes a tensor that does not overlap its input")
+    call("ubpl_warp_views", src, N, C, H, W, mat, V, out)
+    return out
+
+
+def decode_heatmaps_views(hm, sv, sb, V, N, K, H, W, mat, swap=None, perm=None, tinv=None, want_merged=False,
+                          out=None):
+    """Multi-view decode (ubpl_decode_heatmaps_views): hm is a tensor whose first element is view
+    0's map (0, 0), view stride sv and batch stride sb floats — a [V,N,K,H,W] buffer, or the last
+    stacks of a view-major [V*N,S,K,H,W] output through a view at an element offset.  mat: device
+    float32 [V,6] (view_matrices' hm_mat); swap: device int32 [V] or None; perm: device int32 [K]
+    or None.  1 <= V <= 16.
+    -> (raw [N,K,2], preds [N,K,2] or None, scores [N,K], merged [N,K,H,W] or None);
+    out = (raw, preds, scores, merged): write into these instead of allocating."""
+    if not 1 <= V <= MAX_VIEWS:
+        raise ValueError("ubpl_amd: decode_heatmaps_views takes 1 to %d views, got %d" % (MAX_VIEWS, V))
+    _chk(hm, "hm")
+    need = (V - 1) * sv + (N - 1) * sb + K * H * W
+    if sv < 0 or sb < 0 or hm.numel() < need:
+        raise ValueError("ubpl_amd: hm holds %d floats, %d x %d maps of strides %d, %d need %d"
+                         % (hm.numel(), V, N, sv, sb, need))
+    _chk(mat, "mat")
+    _chk(swap, "swap", torch.int32)
+    _chk(perm, "perm", torch.int32)
+    _chk(tinv, "tinv", torch.float64)
+    if mat is None or mat.numel() != V * 6:
+        raise ValueError("ubpl_amd: mat is [V,6], one pixel matrix per view")
+    if swap is not None and swap.numel() != V:
+        raise ValueError("ubpl_amd: swap has %d entries for %d views" % (swap.numel(), V))
+    if perm is not None and perm.numel() != K:
+        raise ValueError("ubpl_amd: perm has %d entries for %d joints" % (perm.numel(), K))
+    dev = hm.device
+    if out is not None:
+        raw, preds, scores, merged = out
+    else:
+        raw = torch.empty((N, K, 2), device=dev, dtype=F32)
+        preds = torch.empty((N, K, 2), device=dev, dtype=F32) if tinv is not None else None
+        scores = torch.empty((N, K), device=dev, dtype=F32)
+        merged = torch.empty((N, K, H, W), device=dev, dtype=F32) if want_merged else None
+    call("ubpl_decode_heatmaps_views", hm, int(sv), int(sb), V, N, K, H, W, mat, swap, perm, tinv, merged, raw, preds,
+         scores)
+    return raw, preds, scores, merged
+
+
 def fliplr(x, out=None):
     """ProcessUtils.image_fliplr on device planes: x [..., H, W] -> x mirrored along W
     (out: a different tensor of x's size)."""

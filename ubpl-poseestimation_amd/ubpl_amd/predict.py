@@ -32,8 +32,18 @@ ones: after each network's decode one ubpl_refine_peaks launch on the same heatm
 218-228, or the distribution-aware Taylor step), inside the same graph.  The default
 "none" launches and returns exactly what it did without the option.
 
+`Predictor(tta=[(angle_deg, zoom), ...])` is multi-view test-time augmentation: the reference
+computes a warp matrix per augmented view and can warp heatmaps back (utils/augment.py:158-164
+affine_getWarpmat, :36-47 affine_back2) but only draws with it (projects/MT_UBPL.py:186-205).
+Here ubpl_warp_views fills one view-major batch, each network runs once on it, and
+ubpl_decode_heatmaps_views warps the views' last stacks back, averages them over the views that
+cover each pixel and decodes the merged maps, which refine and pseudo_label then read (the
+convention: DESIGN.md §4 "Multi-view decode").  The default None launches and returns exactly
+what it did without the option.
+
 There is no CPU fallback.
 """
+import math
 import os
 from collections import OrderedDict
 
@@ -47,11 +57,12 @@ class _Slot:
     """Static buffers of one (batch size, resolution, heatmaps wanted) and, once
     captured, the graph that maps its inputs to its outputs."""
 
-    def __init__(self, M, N, K, R, flip, want_hm, dev, refine=False):
+    def __init__(self, M, N, K, R, flip, want_hm, dev, refine=False, views=None):
         H = W = R // 4
         f32 = dict(device=dev, dtype=torch.float32)
         self.N, self.H, self.W = N, H, W
-        self.batch = torch.zeros((2 * N if flip else N, 3, R, R), **f32)
+        # (views: the view count of Predictor(tta=...), mirrored ones included; view-major rows)
+        self.batch = torch.zeros(((2 * N if flip else N) if views is None else views * N, 3, R, R), **f32)
         self.imgs = self.batch[:N]
         self.tinv = torch.zeros((N, 6), device=dev, dtype=torch.float64)
         self.raw = torch.zeros((M, N, K, 2), **f32)
@@ -78,8 +89,8 @@ class _PseudoSlot(_Slot):
     (the ensemble kernel reads them in place), the ensemble outputs and the threshold.
     One slot serves calls with and without return_heatmaps."""
 
-    def __init__(self, M, N, K, R, flip, dev, refine=False):
-        super().__init__(M, N, K, R, flip, True, dev, refine)
+    def __init__(self, M, N, K, R, flip, dev, refine=False, views=None):
+        super().__init__(M, N, K, R, flip, True, dev, refine, views)
         f32 = dict(device=dev, dtype=torch.float32)
         self.thr = torch.zeros(1, **f32)
         self.ens_raw = torch.zeros((N, K, 2), **f32)
@@ -116,6 +127,29 @@ def check_refine(refine, blur_sigma):
     return refine, Kn.blur_taps(blur_sigma if refine == "taylor" else 0.0)
 
 
+def check_tta(tta, flip_test):
+    """The tta / flip_test arguments -> None, or the views as a list of (angle_deg, zoom) floats.
+    The first view is the image itself; with the flip test every view is run mirrored as well."""
+    if tta is None:
+        return None
+    try:
+        views = [(float(a), float(z)) for a, z in tta]
+    except (TypeError, ValueError):
+        raise ValueError("ubpl_amd: tta is a list of (angle_deg, zoom) pairs, got %r" % (tta,))
+    if not views or views[0] != (0.0, 1.0):
+        raise ValueError("ubpl_amd: the first tta view is the image itself, (0, 1)")
+    for a, z in views:
+        if not (math.isfinite(a) and math.isfinite(z)):
+            raise ValueError("ubpl_amd: a tta view is a finite (angle_deg, zoom), got (%r, %r)" % (a, z))
+        if not 0.5 <= z <= 2.0:
+            raise ValueError("ubpl_amd: a tta zoom lies in [0.5, 2], got %r" % z)
+    V = len(views) * (2 if flip_test else 1)
+    if V > Kn.MAX_VIEWS:
+        raise ValueError("ubpl_amd: %d tta views%s make %d, at most %d"
+                         % (len(views), " with their mirrors" if flip_test else "", V, Kn.MAX_VIEWS))
+    return views
+
+
 def assemble_kps(ens_preds, selected):
     """[N,K,2] image coordinates + [N,K] bool -> [N,K,3] (x, y, selected as 0/1), the
     meta["kpsMap"] layout."""
@@ -124,7 +158,7 @@ def assemble_kps(ens_preds, selected):
 
 class Predictor:
     """Predictor(models, flip_test=False, flip_pairs=None, max_batch=32, max_graphs=4, graph=None,
-              refine="none", blur_sigma=DEFAULT_BLUR_SIGMA)
+              refine="none", blur_sigma=DEFAULT_BLUR_SIGMA, tta=None)
 
     models      one StackedHourglass or a list (the teachers), same k, one device;
     flip_test   average each heatmap with the flipped-back heatmap of the mirrored image;
@@ -140,7 +174,14 @@ class Predictor:
                 preds_mean_sub and refine_rule (pseudo_label: also ens_raw_sub, ens_preds_sub,
                 ens_refine_rule, kps_sub); raw, preds and preds_mean keep their integer meaning;
     blur_sigma  "taylor" only: sigma in heatmap cells of the Gaussian blur of the window around
-                the peak (0: none; at most 2.0).
+                the peak (0: none; at most 2.0);
+    tta         None: one view (two with the flip test), as ever.  A list of (angle_deg, zoom)
+                whose first entry is (0, 1): test-time augmentation — every network runs on all
+                the views in one batch (ubpl_warp_views makes them; with flip_test each also
+                mirrored, at most 16 in all), and ubpl_decode_heatmaps_views warps their heatmaps
+                back, averages them over the views that cover each pixel and decodes the merged
+                maps, which `heatmaps`, refine and pseudo_label then read.  Chunks shrink so that
+                the forward batch stays within 2 max_batch.
 
     Snapshot semantics: construction and refresh() copy the networks' parameters and
     running statistics into private frozen weight sets; training steps, EMA updates or
@@ -149,8 +190,9 @@ class Predictor:
     never touched."""
 
     def __init__(self, models, flip_test=False, flip_pairs=None, max_batch=32, max_graphs=4, graph=None,
-                 refine="none", blur_sigma=DEFAULT_BLUR_SIGMA):
+                 refine="none", blur_sigma=DEFAULT_BLUR_SIGMA, tta=None):
         self.refine, taps = check_refine(refine, blur_sigma)
+        self.tta = check_tta(tta, flip_test)
         self.blur_sigma = float(blur_sigma) if refine == "taylor" else None
         _lib.require_gpu()
         from .hourglass import StackedHourglass
@@ -169,6 +211,11 @@ class Predictor:
             self.perm = Kn.flip_perm(self.k, flip_pairs).to(self.device)
         self.taps = None if taps is None else taps.to(self.device)
         self.max_batch, self.max_graphs = int(max_batch), int(max_graphs)
+        self.views = None
+        if self.tta is not None:
+            self.views = len(self.tta) * (2 if self.flip_test else 1)
+            self.max_batch = min(self.max_batch, max(1, 2 * self.max_batch // self.views))
+            self._view_mats = {}                    # resolution -> device (img_mat, hm_mat, swap)
         self.use_graph = os.environ.get("UBPL_PREDICT_GRAPH", "1") != "0" if graph is None else bool(graph)
         self._slots = OrderedDict()
         self._sets = None
@@ -199,6 +246,8 @@ class Predictor:
     def _run(self, s):
         """The device work of one batch, on the current stream: static inputs of slot s
         -> its static outputs."""
+        if self.tta is not None:
+            return self._run_views(s)
         N, K = s.N, self.k
         if self.flip_test:
             Kn.fliplr(s.imgs, out=s.batch[N:])
@@ -222,8 +271,37 @@ class Predictor:
         if s.refine:
             s.mean_sub.copy_(torch.stack(list(s.preds_sub), -1).mean(-1))
 
+    def _run_views(self, s):
+        """_run with test-time augmentation: the views of s.imgs fill the rest of the view-major
+        batch, every network runs once on all of them, and the multi-view decode merges the last
+        stacks into s.heatmaps[mi], which the refinement then reads as plain maps."""
+        N, K, V = s.N, self.k, self.views
+        R = s.batch.shape[2]
+        if R not in self._view_mats:
+            img_mat, hm_mat, swap = Kn.view_matrices(self.tta, self.flip_test, R, R // 4)
+            self._view_mats[R] = (img_mat.to(self.device), hm_mat.to(self.device),
+                                  swap.to(self.device) if self.flip_test else None)
+        img_mat, hm_mat, swap = self._view_mats[R]
+        if V > 1:
+            Kn.warp_views(s.imgs, img_mat[1:], out=s.batch[N:])
+        for mi, (m, ws) in enumerate(zip(self.models, self._sets)):
+            o = m.forward_frozen(s.batch, ws)                       # [V*N, S, K, H, W]
+            S, H, W = o.shape[1], o.shape[3], o.shape[4]
+            if (H, W) != (s.H, s.W):
+                raise RuntimeError("ubpl_amd: heatmaps %dx%d, expected %dx%d" % (H, W, s.H, s.W))
+            sb, last = S * K * H * W, (S - 1) * K * H * W
+            Kn.decode_heatmaps_views(o.reshape(-1)[last:], N * sb, sb, V, N, K, H, W, hm_mat, swap, self.perm, s.tinv,
+                                     out=(s.raw[mi], s.preds[mi], s.scores[mi], s.heatmaps[mi]))
+            if s.refine:
+                Kn.refine_peaks(s.heatmaps[mi], None, K * H * W, N, K, H, W, None, s.raw[mi], self.refine, self.taps,
+                                s.tinv, out=(s.raw_sub[mi], s.preds_sub[mi], s.rule[mi]))
+        s.mean.copy_(torch.stack(list(s.preds), -1).mean(-1))       # projects/MT_UBPL.py:387
+        if s.refine:
+            s.mean_sub.copy_(torch.stack(list(s.preds_sub), -1).mean(-1))
+
     def _slot(self, N, R, want_hm, pseudo=False):
         # (pseudo_label's slots carry a key of their own: predict's graphs and buffers stay its own)
+        want_hm = want_hm or self.tta is not None                   # (the merged maps are the decode's output)
         key = ("pseudo", N, R) if pseudo else (N, R, want_hm)
         s = self._slots.get(key)
         if s is not None:
@@ -236,7 +314,8 @@ class Predictor:
             torch.cuda.empty_cache()
         a = (len(self.models), N, self.k, R, self.flip_test)
         on = self.refine != "none"
-        s = self._slots[key] = _PseudoSlot(*a, self.device, on) if pseudo else _Slot(*a, want_hm, self.device, on)
+        s = self._slots[key] = (_PseudoSlot(*a, self.device, on, self.views) if pseudo else
+                                _Slot(*a, want_hm, self.device, on, self.views))
         return s, True
 
     def _launch(self, s, new, run):
@@ -297,7 +376,7 @@ class Predictor:
         """imgs float32 [N,3,R,R] (host or device) -> dict of device tensors, the caller's own:
         raw [M,N,K,2] 1-based heatmap coordinates, scores [M,N,K], preds [M,N,K,2] and
         preds_mean [N,K,2] in image coordinates (None without center / scale), and with
-        return_heatmaps heatmaps [M,N,K,H,W], the (flip-merged) last-stack maps; M networks.
+        return_heatmaps heatmaps [M,N,K,H,W], the (flip- or view-merged) last-stack maps; M networks.
         out_res: the resolution of the inverse transform (default: the heatmaps')."""
         imgs, tinv = self._inputs("predict", imgs, center, scale, out_res)
         N = imgs.shape[0]
@@ -402,7 +481,8 @@ class Predictor:
         meta["scale"] (the shape validate takes; args.outRes, when given, is the resolution of
         the inverse transform).  -> a host dict of plain lists, sample-major: predsArraies
         (the reference's key, projects/MT_UBPL.py:120: [x, y] per joint from ens_preds; with
-        refine on from ens_preds_sub, and the dict records "refine" and "blur_sigma"),
+        refine on from ens_preds_sub, and the dict records "refine" and "blur_sigma"; with tta
+        set it records "tta", the views),
         selected, ens_score, spread [N][K], disagree [N][M][K], thr, rule and
         selected_fraction [K].  Single process only, as validate."""
         from . import dist as D
@@ -426,6 +506,8 @@ class Predictor:
              "selected_fraction": sel.float().mean(0).tolist() if sel.numel() else []}
         if on:
             d.update({"refine": self.refine, "blur_sigma": self.blur_sigma})
+        if self.tta is not None:
+            d["tta"] = [list(v) for v in self.tta]
         return d
 
     def validate(self, loader, args):
