@@ -204,6 +204,66 @@ int ubpl_warp_views(const float* src, int N, int C, int H, int W, const float* m
 int ubpl_decode_heatmaps_views(const float* hm, int64_t sv, int64_t sb, int V, int N, int K, int H, int W,
                                const float* mat, const int* swap, const int* perm, const double* tinv,
                                float* merged, float* raw, float* preds, float* scores, void* stream);
+/* View-consistency uncertainty of multi-view predictions: the reference's
+ * geometric pseudo-label uncertainty (utils/business.py: pseudo_cal_unc
+ * :220-234, _initKSample :302-318, _calKSampleExterData :320-346,
+ * pseudo_filter_mixUnc :237-264, assess_pseudo_unc2 :109-161;
+ * utils/process.py:53-68 coord_distance / coord_avgDistance) from the per-view
+ * peaks of M members (teachers) on V views of N samples, in one launch.
+ * Member m's point of view v, sample n, output joint k is the pair of floats
+ * at raw + m*sm + ((v*N + n)*K + k')*2 (sm: the member stride in floats; per
+ * member a view-major [V*N,K,2] block as ubpl_decode_heatmaps_flip or
+ * ubpl_refine_peaks writes it with N' = V*N), k' = perm[k] where swap[v] != 0,
+ * else k (swap int32 [V], null = none; perm int32 [K], null = identity, an
+ * entry outside [0, K) falls back to k: ubpl_decode_heatmaps_views' rule).
+ * Points are 1-based heatmap coordinates in the view's own frame, integer or
+ * sub-pixel; (0,0) = no peak.  1 <= M <= 8 and 2 <= V <= 16
+ * (hipErrorInvalidValue otherwise).  back [V,6] f32: view heatmap pixel ->
+ * original-frame heatmap pixel, the f64 inverse of ubpl_decode_heatmaps_views'
+ * mat rounded once (kernels.view_back_matrices).  dist_thr: device f32[1], read
+ * by the kernel, so a captured graph serves every threshold.  Every product,
+ * sum, quotient and square root below is its own f32 rounding (no FMA) unless
+ * f64 is named; every comparison is false on a NaN.
+ * Per point:  u = raw_x - 1, v = raw_y - 1;  ox = (b0*u + b1*v) + b2,
+ *   oy = (b3*u + b4*v) + b5.  Without tinv the point is p = (ox + 1, oy + 1),
+ *   heatmap cells.  With tinv [N,6] it is ubpl_refine_peaks' preds_sub
+ *   expression at u = ox, v = oy: (t0 u + t1 v + t2 + 1, t3 u + t4 v + t5 + 1)
+ *   in f64 with the decode's un-fused order, rounded to f32, not truncated:
+ *   image coordinates.  pts [M,V,N,K,2] = p, whatever its legality.  A point is
+ *   legal iff raw is not (0,0), both coordinates of p are finite and, with
+ *   tinv, both are >= 0 (coord_legal, business.py:31).
+ * Per member (m, n, k):  legal [M,N,K] = 1 iff all V points are legal
+ *   (_checkGroupLegal), else 0.  With d(p, q) = sqrtf(dx*dx + dy*dy):
+ *   int_dist [M,N,K] = (sum of d over the V(V-1)/2 view pairs (a, b), a < b, in
+ *   itertools.combinations order, sequentially from 0) / (float)pairs
+ *   (coord_avgDistance); aug_coord [M,N,K,2] = (sequential sum of the V points
+ *   from 0) / (float)V (coord_aug, :313).  Not legal: int_dist = mix_dist = unc
+ *   = 999 (the reference's sentinel), aug_coord = (-1,-1), select = 0.
+ * Per (n, k), over the member pairs a < b with both legal, ascending, each a
+ *   sequential sum from 0 divided by (float)count:  ext_dist [N,K] = mean of
+ *   d(p_a0, p_b0), the view-0 points (extDist, :322); aext_dist [N,K] = mean of
+ *   d(aug_coord_a, aug_coord_b) (aExtDist, :323); ext_views [N,K] = mean over
+ *   pairs of ((sum over views v of d(p_av, p_bv), sequentially from 0) /
+ *   (float)V) (assess_pseudo_unc2's extDist, :144-149).  For M = 2 each is the
+ *   reference's value.  M >= 2 and no legal pair: all three 999; M = 1: all 0.
+ * Per legal member:  mix_dist [M,N,K] = int_dist + (ext_dist > 0 ? (ext_dist +
+ *   aext_dist)/2 : aext_dist) (:328); unc [M,N,K] = 1 - expf(-mix_dist/5)
+ *   (_calUncValue); select [M,N,K] = 1 iff int_dist <= t, ext_dist <= t,
+ *   aext_dist <= t (:331-345) and mix_dist <= 3*t, t = dist_thr[0], else 0.
+ *   1 - exp(-x/5) is monotonic, so the last condition is the reference's
+ *   unc <= _calUncValue(3 * distThrMax) (:242-247) decided on the distance,
+ *   where no rounding of expf can flip it.
+ * The reference's running average over epochs (_lma_variables, :397-406) is
+ * the identity on a first call, which is what one inference pass is: the
+ * *_lma values are the values themselves and no history is kept.  The scores
+ * of _initKSample (:309-311) index batch row 0 and feed no distance: left out.
+ * tinv and every output but select are nullable.  No atomics, fixed summation
+ * orders: repeated launches give equal bits. */
+/*@ raw:f32[(M-1)*sm+(int64_t)V*N*K*2] back:f32[V*6] swap:i32[V] perm:i32[K] tinv:f64[N*6] dist_thr:f32[1] pts:f32[(int64_t)M*V*N*K*2] legal:f32[(int64_t)M*N*K] int_dist:f32[(int64_t)M*N*K] aug_coord:f32[(int64_t)M*N*K*2] ext_dist:f32[N*K] aext_dist:f32[N*K] ext_views:f32[N*K] mix_dist:f32[(int64_t)M*N*K] unc:f32[(int64_t)M*N*K] select:f32[(int64_t)M*N*K] */
+int ubpl_view_uncertainty(const float* raw, int64_t sm, int M, int V, int N, int K, const float* back,
+                          const int* swap, const int* perm, const double* tinv, const float* dist_thr, float* pts,
+                          float* legal, float* int_dist, float* aug_coord, float* ext_dist, float* aext_dist,
+                          float* ext_views, float* mix_dist, float* unc, float* select, void* stream);
 /* EvaluationUtils.acc_pck (utils/evaluation.py:91-139).  errs/accs [K+1];
  * hits/valid [K] int32 (nullable) for cross-rank aggregation. */
 /*@ preds:f32[N*K*2] gts:f32[N*K*3] errs:f32[K+1] accs:f32[K+1] hits:i32[K] valid:i32[K] */

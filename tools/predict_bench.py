@@ -50,6 +50,18 @@ differ in tta / flip_test alone:
 
 Same warm-up, rounds and report; v1 and none must agree bit for bit before anything is timed.
 A Predictor with tta keeps its forward batch within 2 max_batch images, so larger B run in chunks.
+
+--mode unc times what the view-consistency uncertainty adds, on ONE pair of teachers and two
+Predictors per view set that differ in the option alone:
+
+  (v5_off / v5_on)    pseudo_label with tta = three zooms + two rotations, uncertainty off / on
+                      (on: rule "uncertainty" at --dist-thr);
+  (v10_off / v10_on)  the same views with flip_test;
+  (p5_off / p5_on)    predict of ONE teacher on the five views, uncertainty off / on — p5_off is
+                      --mode tta's v5.
+
+Same warm-up, rounds and report; off and on must agree bit for bit on every key they share
+before anything is timed.
 """
 import argparse
 import json
@@ -184,6 +196,56 @@ def tta_main(a):
     print(line)
 
 
+def unc_main(a):
+    from ubpl_amd import Predictor, _lib, kernels as Kn
+    _lib.require_gpu()
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    gen = torch.Generator().manual_seed(1)
+    models = [teacher(a, seed, gen, dev) for seed in (0, 1)]
+    kw = refine_kw(a)
+    views = TTA_ZOOMS + TTA_ROTATIONS
+    P = {}
+    for name, flip in (("v5", False), ("v10", True)):
+        P[name + "_off"] = Predictor(models, tta=views, flip_test=flip, **kw)
+        P[name + "_on"] = Predictor(models, tta=views, flip_test=flip, uncertainty=True, **kw)
+    call = {n: (lambda x, c, s, p=p, on=n.endswith("_on"):
+                p.pseudo_label(x, c, s, thr=a.thr, **({"rule": "uncertainty", "dist_thr": a.dist_thr} if on else {})))
+            for n, p in P.items()}
+    P["p5_off"] = Predictor(models[0], tta=views, **kw)
+    P["p5_on"] = Predictor(models[0], tta=views, uncertainty=True, **kw)
+    for n in ("p5_off", "p5_on"):
+        call[n] = lambda x, c, s, p=P[n]: p.predict(x, c, s)
+    rows = []
+    for B in [int(b) for b in a.batches.split(",")]:
+        x = (torch.rand(B, 3, a.res, a.res, generator=gen) - 0.5).to(dev)
+        center = torch.full((B, 2), a.res / 2.0)
+        scale = torch.full((B,), a.res / 200.0)
+        outs = {n: f(x, center, scale) for n, f in call.items()}
+        row = {"B": B, "chunk": {n: min(B, p.max_batch) for n, p in P.items()}}
+        for v in ("v5", "v10", "p5"):
+            off, on = outs[v + "_off"], outs[v + "_on"]
+            if not all(torch.equal(on[k], off[k]) for k in off if k not in ("selected", "kps", "kps_sub")):
+                raise SystemExit("predict_bench: uncertainty=True changes a shared output (%s, B=%d)" % (v, B))
+            row[v + "_legal_fraction"] = round(float(on["view_legal"].float().mean()), 4)
+            if "selected" in on:
+                row[v + "_selected_fraction"] = round(float(on["selected"].float().mean()), 4)
+        row.update(measure({n: (lambda f=f: f(x, center, scale)) for n, f in call.items()}, a))
+        for v in ("v5", "v10", "p5"):
+            row[v + "_added_us"] = round((row[v + "_on_ms"] - row[v + "_off_ms"]) * 1e3, 1)
+            row[v + "_on_over_off"] = round(row[v + "_on_ms"] / row[v + "_off_ms"], 4)
+        rows.append(row)
+    out = {"tool": "predict_bench", "mode": "unc", "model": "HG%d" % a.stacks, "teachers": len(models), "k": a.k,
+           "res": a.res, "views": {"v5": 5, "v10": 10, "p5": 5}, "zooms": TTA_ZOOMS, "rotations": TTA_ROTATIONS,
+           "refine": a.refine, "thr": a.thr, "dist_thr": a.dist_thr, "precision": Kn.conv_precision_name(),
+           "repeats": a.repeats, "device": torch.cuda.get_device_name(0), "rows": rows}
+    line = json.dumps(out)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
 def pseudo_main(a):
     from ubpl_amd import Predictor, _lib, kernels as Kn
     from ubpl_amd.hourglass import StackedHourglass
@@ -249,11 +311,14 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--window", type=float, default=0.25, help="seconds of work per variant per round")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--mode", default="predict", choices=["predict", "pseudo", "refine", "tta"])
+    ap.add_argument("--mode", default="predict", choices=["predict", "pseudo", "refine", "tta", "unc"])
     ap.add_argument("--refine", default="none", choices=["none", "quarter", "taylor"])
     ap.add_argument("--blur-sigma", type=float, default=None, help="taylor's blur (default: the Predictor's)")
     ap.add_argument("--thr", type=float, default=0.95, help="--mode pseudo: the score threshold (<= 0: each batch's median ensemble score)")
+    ap.add_argument("--dist-thr", type=float, default=8.0, help="--mode unc: the distance threshold, image pixels")
     a = ap.parse_args()
+    if a.mode == "unc":
+        return unc_main(a)
     if a.mode == "pseudo":
         return pseudo_main(a)
     if a.mode == "refine":

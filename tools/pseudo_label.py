@@ -8,7 +8,8 @@ split has ground truth, prints the selection rate and the share of valid joints 
 pck_thr of the truth, for the selected joints and for all of them.
 
     python tools/pseudo_label.py [--ckpt ckpts/checkpoint_best.pth.tar] [--model HG2]
-                                 [--thr 0.95] [--rule unanimous|ensemble] [--flip] [--out FILE]
+                                 [--thr 0.95] [--rule unanimous|ensemble|uncertainty] [--dist-thr a,b,c]
+                                 [--flip] [--out FILE]
                                  [--refine none|quarter|taylor|all] [--blur-sigma S]
                                  [--train-epochs E] [--record FILE] [--tta rows|A:Z,A:Z,...]
 
@@ -23,6 +24,11 @@ first by E epochs of tools/mouse_pck.py's experiment (once, shared by every vari
 (with --flip every view also mirrored).  --tta rows labels the split once per row of views —
 none; flip; three zooms; three zooms + two rotations; those five with flip — for every refine
 variant asked for (--refine takes a comma-separated list too), with the same weights.
+
+--rule uncertainty --dist-thr a,b,c: the view-consistency rule (Predictor(uncertainty=True), so
+rows of fewer than 2 views are left out), labelled once per distance threshold (image pixels)
+on the same Predictor.  --rule takes a comma-separated list, e.g. ensemble,uncertainty, to put
+the score rule beside it with the same weights and views.
 
 Reads tests/golden/mouse_100_500_0.3/ (tools/pack_mouse.py).  Untrained networks select
 next to nothing at the default threshold; that is the expected output without --ckpt.
@@ -71,7 +77,8 @@ def main():
     ap.add_argument("--model", default="HG2")
     ap.add_argument("--teachers", type=int, default=2)
     ap.add_argument("--thr", type=float, default=0.95)
-    ap.add_argument("--rule", default="unanimous")
+    ap.add_argument("--rule", default="unanimous", help="unanimous, ensemble, uncertainty, or a comma-separated list")
+    ap.add_argument("--dist-thr", default=None, help="rule uncertainty: distance thresholds in image pixels, a,b,c")
     ap.add_argument("--flip", action="store_true")
     ap.add_argument("--inferBS", type=int, default=32)
     ap.add_argument("--limit", type=int, default=0, help="label only the first batches up to this many images")
@@ -85,7 +92,16 @@ def main():
 
     from ubpl_amd import Predictor, _lib, checkpoint, mouse
     from ubpl_amd.hourglass import pose_model
-    from ubpl_amd.predict import DEFAULT_BLUR_SIGMA
+    from ubpl_amd.predict import DEFAULT_BLUR_SIGMA, check_rule
+    rules = []                                   # (rule, dist_thr or None), one labelling each
+    for rule in a.rule.split(","):
+        if check_rule(rule) != "uncertainty":
+            rules.append((rule, None))
+            continue
+        if not a.dist_thr:
+            ap.error("--rule uncertainty needs --dist-thr (the reference ships no default)")
+        rules += [(rule, float(t)) for t in a.dist_thr.split(",")]
+    unc = any(r == "uncertainty" for r, _ in rules)
     _lib.require_gpu()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
@@ -116,14 +132,20 @@ def main():
     rows_of_views = tta_rows(a.tta, a.flip)
     vargs = types.SimpleNamespace(outRes=data.outRes, pck_ref=data.pck_ref, pck_thr=data.pck_thr)
     rows = []
-    for refine, sg, (row_name, views, flip) in [(r, g, t) for r, g in variants for t in rows_of_views]:
-        P = Predictor(teachers, flip_test=flip, max_batch=a.inferBS, refine=refine, blur_sigma=sg, tta=views)
-        d = P.label_pool(loader, types.SimpleNamespace(outRes=data.outRes), thr=a.thr, rule=a.rule)
+    if unc:                                      # view consistency needs views to compare
+        rows_of_views = [t for t in rows_of_views if t[1] is not None and len(t[1]) * (2 if t[2] else 1) >= 2]
+    several = len(variants) * len(rows_of_views) * len(rules) > 1
+    for refine, sg, (row_name, views, flip), (rule, dist_thr) in [(r, g, t, u) for r, g in variants
+                                                                  for t in rows_of_views for u in rules]:
+        P = Predictor(teachers, flip_test=flip, max_batch=a.inferBS, refine=refine, blur_sigma=sg, tta=views,
+                      uncertainty=unc)
+        d = P.label_pool(loader, types.SimpleNamespace(outRes=data.outRes), thr=a.thr, rule=rule, dist_thr=dist_thr)
         d["source"] = {"ckpt": a.ckpt, "model": a.model, "teachers": a.teachers, "flip_test": flip,
                        "split": "Mouse_100_500_0.3 valid", "images": len(d["predsArraies"]), "trained": trained}
-        out = a.out if len(variants) * len(rows_of_views) == 1 else "%s.%s%s%s.json" % (
+        out = a.out if not several else "%s.%s%s%s%s.json" % (
             os.path.splitext(a.out)[0], refine, "_s%g" % sg if refine == "taylor" else "",
-            "" if len(rows_of_views) == 1 else ".v%d" % (P.views or (2 if flip else 1)))
+            "" if len(rows_of_views) == 1 else ".v%d" % (P.views or (2 if flip else 1)),
+            "" if len(rules) == 1 else ".%s%s" % (rule, "" if dist_thr is None else "_%g" % dist_thr))
         checkpoint.save_pseudo_data(d, out)
         preds = torch.tensor(d["predsArraies"])
         sel = torch.tensor(d["selected"])
@@ -134,13 +156,20 @@ def main():
         rows.append({"out": out, "refine": refine, "blur_sigma": sg if refine == "taylor" else None,
                      "views": row_name, "tta": views, "flip_test": flip,
                      "forward_passes_per_image": P.views or (2 if flip else 1),
-                     "images": len(preds), "thr": a.thr, "rule": a.rule,
+                     "images": len(preds), "thr": a.thr, "rule": rule, "dist_thr": dist_thr,
                      "selected_fraction": round(float(sel.float().mean()), 4),
                      "selected_fraction_per_joint": [round(v, 4) for v in d["selected_fraction"]],
                      "within_pck_thr_all": share(valid), "within_pck_thr_selected": share(valid & sel),
                      "mean_pixel_error": float((preds - gts[..., :2]).norm(dim=-1)[valid].mean()),
                      "validate_pck": [round(v[-1], 4) for v in accs],     # teacher 1, ..., their mean
                      "trained": a.ckpt is not None or trained is not None})
+        if unc:                                  # how large the distances are, legal members only (image pixels)
+            legal = torch.tensor(d["int_dist"]) < 999
+            q = lambda t: [round(float(v), 3) for v in torch.quantile(t, torch.tensor([0.25, 0.5, 0.75]))] \
+                if t.numel() else None
+            rows[-1].update({"legal_member_fraction": round(float(legal.float().mean()), 4),
+                             "int_dist_quartiles": q(torch.tensor(d["int_dist"])[legal]),
+                             "ext_dist_quartiles": q(torch.tensor(d["ext_dist"])[torch.tensor(d["ext_dist"]) < 999])})
         print(json.dumps(rows[-1]))
     if a.record:
         os.makedirs(os.path.dirname(os.path.abspath(a.record)), exist_ok=True)

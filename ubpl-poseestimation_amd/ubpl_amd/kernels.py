@@ -456,6 +456,76 @@ def decode_heatmaps_views(hm, sv, sb, V, N, K, H, W, mat, swap=None, perm=None, 
     return raw, preds, scores, merged
 
 
+# ---- view-consistency uncertainty (csrc/uncertainty.hip; the rule: include/ubpl_hip.h)
+def view_back_matrices(hm_mat):
+    """view_matrices' hm_mat [V,6] (original-frame heatmap pixel -> view heatmap pixel) -> host
+    float32 [V,6], view heatmap pixel -> original-frame heatmap pixel: the inverse of each (float32)
+    matrix taken in float64 and rounded once.  ValueError on a singular matrix."""
+    m = _mat6(hm_mat.detach().cpu() if torch.is_tensor(hm_mat) else hm_mat)
+    det = m[:, 0] * m[:, 4] - m[:, 1] * m[:, 3]
+    if not bool(((det != 0) & torch.isfinite(det)).all()):
+        raise ValueError("ubpl_amd: view_back_matrices takes invertible pixel matrices")
+    out = torch.empty_like(m)
+    out[:, 0], out[:, 1] = m[:, 4] / det, -m[:, 1] / det
+    out[:, 3], out[:, 4] = -m[:, 3] / det, m[:, 0] / det
+    out[:, 2] = -(out[:, 0] * m[:, 2] + out[:, 1] * m[:, 5])
+    out[:, 5] = -(out[:, 3] * m[:, 2] + out[:, 4] * m[:, 5])
+    return out.to(F32)
+
+
+UNC_OUTPUTS = ("pts", "legal", "int_dist", "aug_coord", "ext_dist", "aext_dist", "ext_views", "mix_dist", "unc",
+               "select")
+
+
+def view_uncertainty(raw, sm, M, V, N, K, back, dist_thr, swap=None, perm=None, tinv=None, out=None):
+    """View-consistency uncertainty (ubpl_view_uncertainty; utils/business.py pseudo_cal_unc /
+    assess_pseudo_unc2): raw is a tensor whose first element is member 0's point of view 0, sample
+    0, joint 0 — per member a view-major [V*N,K,2] block of 1-based view-frame peaks, member stride
+    sm floats.  back: device float32 [V,6] (view_back_matrices(hm_mat).to(device)); dist_thr: device
+    float32 [1] (read by the kernel); swap: device int32 [V] or None; perm: device int32 [K] or
+    None; tinv: device float64 [N,6] or None (points in heatmap cells).  1 <= M <= 8, 2 <= V <= 16.
+    -> (pts [M,V,N,K,2], legal [M,N,K], int_dist [M,N,K], aug_coord [M,N,K,2], ext_dist [N,K],
+        aext_dist [N,K], ext_views [N,K], mix_dist [M,N,K], unc [M,N,K], select [M,N,K] 0/1);
+    out = the same tuple: write into these instead of allocating (select is required)."""
+    if not 1 <= M <= 8:
+        raise ValueError("ubpl_amd: view_uncertainty takes 1 to 8 members, got %d" % M)
+    if not 2 <= V <= MAX_VIEWS:
+        raise ValueError("ubpl_amd: view_uncertainty takes 2 to %d views, got %d" % (MAX_VIEWS, V))
+    _chk(raw, "raw")
+    need = (M - 1) * sm + V * N * K * 2
+    if raw is None or sm < 0 or (M > 1 and sm < V * N * K * 2) or raw.numel() < need:
+        raise ValueError("ubpl_amd: raw holds %d floats, %d members of stride %d with %d x %d x %d points need %d"
+                         % (0 if raw is None else raw.numel(), M, sm, V, N, K, need))
+    _chk(back, "back")
+    _chk(dist_thr, "dist_thr")
+    _chk(swap, "swap", torch.int32)
+    _chk(perm, "perm", torch.int32)
+    _chk(tinv, "tinv", torch.float64)
+    if back is None or back.numel() != V * 6:
+        raise ValueError("ubpl_amd: back is [V,6], one pixel matrix per view")
+    if dist_thr is None or dist_thr.numel() != 1:
+        raise ValueError("ubpl_amd: dist_thr is a device float32 tensor of one element")
+    if swap is not None and swap.numel() != V:
+        raise ValueError("ubpl_amd: swap has %d entries for %d views" % (swap.numel(), V))
+    if perm is not None and perm.numel() != K:
+        raise ValueError("ubpl_amd: perm has %d entries for %d joints" % (perm.numel(), K))
+    if tinv is not None and tinv.numel() != N * 6:
+        raise ValueError("ubpl_amd: tinv has %d entries for %d samples" % (tinv.numel(), N))
+    dev = raw.device
+    if out is not None:
+        pts, legal, int_dist, aug_coord, ext_dist, aext_dist, ext_views, mix_dist, unc, select = out
+    else:
+        e = lambda *s: torch.empty(s, device=dev, dtype=F32)
+        pts, legal, int_dist, aug_coord = e(M, V, N, K, 2), e(M, N, K), e(M, N, K), e(M, N, K, 2)
+        ext_dist, aext_dist, ext_views = e(N, K), e(N, K), e(N, K)
+        mix_dist, unc, select = e(M, N, K), e(M, N, K), e(M, N, K)
+    if select is None:
+        raise ValueError("ubpl_amd: view_uncertainty always writes select")
+    call("ubpl_view_uncertainty", raw, int(sm), M, V, N, K, back, swap, perm, tinv, dist_thr, pts, legal, int_dist,
+         aug_coord, ext_dist, aext_dist, ext_views, mix_dist, unc, select)
+    return pts, legal, int_dist, aug_coord, ext_dist, aext_dist, ext_views, mix_dist, unc, select
+
+
 def fliplr(x, out=None):
     """ProcessUtils.image_fliplr on device planes: x [..., H, W] -> x mirrored along W
     (out: a different tensor of x's size)."""

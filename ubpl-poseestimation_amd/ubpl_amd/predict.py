@@ -41,6 +41,14 @@ cover each pixel and decodes the merged maps, which refine and pseudo_label then
 convention: DESIGN.md §4 "Multi-view decode").  The default None launches and returns exactly
 what it did without the option.
 
+`Predictor(uncertainty=True)` (with tta) keeps what the merge throws away: every network's peak
+on every view (the strided plain decode of the same view-major output, refined when refine is
+on), and one ubpl_view_uncertainty launch inside the same graph folds them into the reference's
+geometric uncertainty (utils/business.py pseudo_cal_unc / assess_pseudo_unc2: how far one
+network's views lie apart, how far the networks lie from one another, unc = 1 - exp(-mixDist/5));
+`pseudo_label(rule="uncertainty", dist_thr=...)` selects on it (DESIGN.md §4 "View-consistency
+uncertainty").  The default False launches and returns exactly what it did without the option.
+
 There is no CPU fallback.
 """
 import math
@@ -57,7 +65,7 @@ class _Slot:
     """Static buffers of one (batch size, resolution, heatmaps wanted) and, once
     captured, the graph that maps its inputs to its outputs."""
 
-    def __init__(self, M, N, K, R, flip, want_hm, dev, refine=False, views=None):
+    def __init__(self, M, N, K, R, flip, want_hm, dev, refine=False, views=None, unc=None):
         H = W = R // 4
         f32 = dict(device=dev, dtype=torch.float32)
         self.N, self.H, self.W = N, H, W
@@ -76,6 +84,21 @@ class _Slot:
             self.preds_sub = torch.zeros((M, N, K, 2), **f32)
             self.rule = torch.zeros((M, N, K), **f32)
             self.mean_sub = torch.zeros((N, K, 2), **f32)
+        self.unc = unc is not None
+        if self.unc:                                # the per-view peaks and their fold (Predictor(uncertainty=True))
+            V = views
+            self.have_tinv = bool(unc)              # (the kernel's tinv is null or not: part of the slot's key)
+            self.raw_views = torch.zeros((M, V * N, K, 2), **f32)
+            self.scores_views = torch.zeros((M, V * N, K), **f32)
+            if refine:
+                self.raw_views_sub = torch.zeros((M, V * N, K, 2), **f32)
+            self.dist_thr = torch.zeros(1, **f32)
+            self.view_preds = torch.zeros((M, V, N, K, 2), **f32)
+            self.aug_coord = torch.zeros((M, N, K, 2), **f32)
+            for name in ("view_legal", "int_dist", "mix_dist", "unc_value", "unc_select"):
+                setattr(self, name, torch.zeros((M, N, K), **f32))
+            for name in ("ext_dist", "aext_dist", "ext_views"):
+                setattr(self, name, torch.zeros((N, K), **f32))
         self.graph = None
 
     def release(self):
@@ -89,8 +112,8 @@ class _PseudoSlot(_Slot):
     (the ensemble kernel reads them in place), the ensemble outputs and the threshold.
     One slot serves calls with and without return_heatmaps."""
 
-    def __init__(self, M, N, K, R, flip, dev, refine=False, views=None):
-        super().__init__(M, N, K, R, flip, True, dev, refine, views)
+    def __init__(self, M, N, K, R, flip, dev, refine=False, views=None, unc=None):
+        super().__init__(M, N, K, R, flip, True, dev, refine, views, unc)
         f32 = dict(device=dev, dtype=torch.float32)
         self.thr = torch.zeros(1, **f32)
         self.ens_raw = torch.zeros((N, K, 2), **f32)
@@ -107,7 +130,7 @@ class _PseudoSlot(_Slot):
 
 
 DEFAULT_BLUR_SIGMA = 1.0
-RULES = ("unanimous", "ensemble")
+RULES = ("unanimous", "ensemble", "uncertainty")
 REFINES = ("none", "quarter", "taylor")
 
 
@@ -150,6 +173,36 @@ def check_tta(tta, flip_test):
     return views
 
 
+def check_uncertainty(uncertainty, views, flip_test):
+    """The uncertainty argument against the checked tta views -> bool.  View consistency needs
+    views to compare: tta with at least 2 in all (mirrored ones included)."""
+    if not uncertainty:
+        return False
+    V = 0 if views is None else len(views) * (2 if flip_test else 1)
+    if V < 2:
+        raise ValueError("ubpl_amd: uncertainty=True compares the views of tta: at least 2 in all, got %s"
+                         % ("tta=None" if views is None else "%d" % V))
+    return True
+
+
+def check_dist_thr(rule, dist_thr, uncertainty):
+    """pseudo_label's rule / dist_thr against Predictor(uncertainty=...) -> dist_thr as a float, or
+    None.  The rule "uncertainty" needs both; the reference ships no default threshold
+    (args.distThrMax), and none is invented here."""
+    if rule == "uncertainty" and not uncertainty:
+        raise ValueError('ubpl_amd: rule "uncertainty" needs Predictor(uncertainty=True)')
+    if dist_thr is None:
+        if rule == "uncertainty":
+            raise ValueError('ubpl_amd: rule "uncertainty" needs dist_thr, a distance in the coordinates of the result')
+        return None
+    if not uncertainty:
+        raise ValueError("ubpl_amd: dist_thr needs Predictor(uncertainty=True)")
+    dist_thr = float(dist_thr)
+    if not dist_thr >= 0:
+        raise ValueError("ubpl_amd: dist_thr is a distance >= 0, got %r" % dist_thr)
+    return dist_thr
+
+
 def assemble_kps(ens_preds, selected):
     """[N,K,2] image coordinates + [N,K] bool -> [N,K,3] (x, y, selected as 0/1), the
     meta["kpsMap"] layout."""
@@ -158,7 +211,7 @@ def assemble_kps(ens_preds, selected):
 
 class Predictor:
     """Predictor(models, flip_test=False, flip_pairs=None, max_batch=32, max_graphs=4, graph=None,
-              refine="none", blur_sigma=DEFAULT_BLUR_SIGMA, tta=None)
+              refine="none", blur_sigma=DEFAULT_BLUR_SIGMA, tta=None, uncertainty=False)
 
     models      one StackedHourglass or a list (the teachers), same k, one device;
     flip_test   average each heatmap with the flipped-back heatmap of the mirrored image;
@@ -182,6 +235,16 @@ class Predictor:
                 back, averages them over the views that cover each pixel and decodes the merged
                 maps, which `heatmaps`, refine and pseudo_label then read.  Chunks shrink so that
                 the forward batch stays within 2 max_batch.
+    uncertainty False: nothing more.  True (needs tta with at least 2 views in all): every network's
+                peak on every view is kept as well — one strided ubpl_decode_heatmaps_flip launch
+                per network on the view-major output, and with refine on one ubpl_refine_peaks —
+                and one ubpl_view_uncertainty launch over all networks, inside the graph, folds
+                them into the reference's view-consistency uncertainty (utils/business.py
+                pseudo_cal_unc).  Results gain view_preds [M,V,N,K,2], view_scores [M,V,N,K] (both in
+                the output joint order), view_legal [M,N,K] bool, int_dist [M,N,K], aug_coord
+                [M,N,K,2], ext_dist, aext_dist, ext_views [N,K], mix_dist and unc [M,N,K]; points
+                and distances in image coordinates when center and scale are given, else in
+                heatmap cells (1-based, as raw).  A slot then also belongs to one of the two.
 
     Snapshot semantics: construction and refresh() copy the networks' parameters and
     running statistics into private frozen weight sets; training steps, EMA updates or
@@ -190,9 +253,10 @@ class Predictor:
     never touched."""
 
     def __init__(self, models, flip_test=False, flip_pairs=None, max_batch=32, max_graphs=4, graph=None,
-                 refine="none", blur_sigma=DEFAULT_BLUR_SIGMA, tta=None):
+                 refine="none", blur_sigma=DEFAULT_BLUR_SIGMA, tta=None, uncertainty=False):
         self.refine, taps = check_refine(refine, blur_sigma)
         self.tta = check_tta(tta, flip_test)
+        self.uncertainty = check_uncertainty(uncertainty, self.tta, flip_test)
         self.blur_sigma = float(blur_sigma) if refine == "taylor" else None
         _lib.require_gpu()
         from .hourglass import StackedHourglass
@@ -216,6 +280,8 @@ class Predictor:
             self.views = len(self.tta) * (2 if self.flip_test else 1)
             self.max_batch = min(self.max_batch, max(1, 2 * self.max_batch // self.views))
             self._view_mats = {}                    # resolution -> device (img_mat, hm_mat, swap)
+        if self.uncertainty:
+            self._back_mats = {}                    # resolution -> device back [V,6] (view cell -> original cell)
         self.use_graph = os.environ.get("UBPL_PREDICT_GRAPH", "1") != "0" if graph is None else bool(graph)
         self._slots = OrderedDict()
         self._sets = None
@@ -295,14 +361,32 @@ class Predictor:
             if s.refine:
                 Kn.refine_peaks(s.heatmaps[mi], None, K * H * W, N, K, H, W, None, s.raw[mi], self.refine, self.taps,
                                 s.tinv, out=(s.raw_sub[mi], s.preds_sub[mi], s.rule[mi]))
+            if s.unc:
+                # every view's own peak: the view-major rows share one batch stride, so the last
+                # stacks are a strided plain decode of V*N samples (each view's frame and joint order)
+                hm_views = o.reshape(-1)[last:]
+                Kn.decode_heatmaps_flip(hm_views, None, sb, V * N, K, H, W, None, None,
+                                        out=(s.raw_views[mi], None, s.scores_views[mi], None))
+                if s.refine:
+                    Kn.refine_peaks(hm_views, None, sb, V * N, K, H, W, None, s.raw_views[mi], self.refine, self.taps,
+                                    None, out=(s.raw_views_sub[mi], None, None))
         s.mean.copy_(torch.stack(list(s.preds), -1).mean(-1))       # projects/MT_UBPL.py:387
         if s.refine:
             s.mean_sub.copy_(torch.stack(list(s.preds_sub), -1).mean(-1))
+        if s.unc:
+            if R not in self._back_mats:
+                self._back_mats[R] = Kn.view_back_matrices(hm_mat).to(self.device)
+            Kn.view_uncertainty(s.raw_views_sub if s.refine else s.raw_views, V * N * K * 2, len(self.models), V, N, K,
+                                self._back_mats[R], s.dist_thr, swap, self.perm, s.tinv if s.have_tinv else None,
+                                out=(s.view_preds, s.view_legal, s.int_dist, s.aug_coord, s.ext_dist, s.aext_dist,
+                                     s.ext_views, s.mix_dist, s.unc_value, s.unc_select))
 
-    def _slot(self, N, R, want_hm, pseudo=False):
+    def _slot(self, N, R, want_hm, pseudo=False, have_tinv=False):
         # (pseudo_label's slots carry a key of their own: predict's graphs and buffers stay its own)
         want_hm = want_hm or self.tta is not None                   # (the merged maps are the decode's output)
         key = ("pseudo", N, R) if pseudo else (N, R, want_hm)
+        if self.uncertainty:                                        # (heatmap cells or image coordinates)
+            key = key + (bool(have_tinv),)
         s = self._slots.get(key)
         if s is not None:
             self._slots.move_to_end(key)
@@ -314,8 +398,9 @@ class Predictor:
             torch.cuda.empty_cache()
         a = (len(self.models), N, self.k, R, self.flip_test)
         on = self.refine != "none"
-        s = self._slots[key] = (_PseudoSlot(*a, self.device, on, self.views) if pseudo else
-                                _Slot(*a, want_hm, self.device, on, self.views))
+        unc = bool(have_tinv) if self.uncertainty else None
+        s = self._slots[key] = (_PseudoSlot(*a, self.device, on, self.views, unc) if pseudo else
+                                _Slot(*a, want_hm, self.device, on, self.views, unc))
         return s, True
 
     def _launch(self, s, new, run):
@@ -339,9 +424,20 @@ class Predictor:
         return {"raw_sub": s.raw_sub.clone(), "preds_sub": s.preds_sub.clone() if have else None,
                 "preds_mean_sub": s.mean_sub.clone() if have else None, "refine_rule": s.rule.clone()}
 
+    def _unc_keys(self, s):
+        """The view-consistency entries of a predict / pseudo_label result (uncertainty on)."""
+        M, V = len(self.models), self.views
+        scores = s.scores_views.reshape(M, V, s.N, self.k).clone()
+        if self.flip_test and self.perm is not None:                # the mirrored views, in the output joint order
+            scores[:, V // 2:] = scores[:, V // 2:][..., self.perm.long()]
+        return {"view_preds": s.view_preds.clone(), "view_scores": scores, "view_legal": s.view_legal > 0,
+                "int_dist": s.int_dist.clone(), "aug_coord": s.aug_coord.clone(), "ext_dist": s.ext_dist.clone(),
+                "aext_dist": s.aext_dist.clone(), "ext_views": s.ext_views.clone(), "mix_dist": s.mix_dist.clone(),
+                "unc": s.unc_value.clone()}
+
     def _predict_chunk(self, imgs, tinv, want_hm):
         N, R = imgs.shape[0], imgs.shape[2]
-        s, new = self._slot(N, R, want_hm)
+        s, new = self._slot(N, R, want_hm, have_tinv=tinv is not None)
         s.imgs.copy_(imgs, non_blocking=True)
         if tinv is not None:
             s.tinv.copy_(tinv, non_blocking=True)
@@ -351,6 +447,8 @@ class Predictor:
                "preds_mean": s.mean.clone() if tinv is not None else None}
         if s.refine:
             out.update(self._sub_keys(s, tinv is not None))
+        if s.unc:
+            out.update(self._unc_keys(s))
         if want_hm:
             out["heatmaps"] = s.heatmaps.clone()
         return out
@@ -387,8 +485,8 @@ class Predictor:
                 outs.append(self._predict_chunk(imgs[a:b], None if tinv is None else tinv[a:b], bool(return_heatmaps)))
         if len(outs) == 1:
             return outs[0]
-        per_sample = ("preds_mean", "preds_mean_sub")
-        return {k: None if outs[0][k] is None else torch.cat([o[k] for o in outs], 0 if k in per_sample else 1)
+        per_sample = ("preds_mean", "preds_mean_sub") + self._PER_SAMPLE_UNC
+        return {k: None if outs[0][k] is None else torch.cat([o[k] for o in outs], self._cat_axis(k, per_sample))
                 for k in outs[0]}
 
     # -- ensemble pseudo-labels --------------------------------------------
@@ -407,17 +505,22 @@ class Predictor:
             Kn.refine_peaks(s.mean_hm, None, K * H * W, N, K, H, W, None, s.ens_raw, self.refine, self.taps, s.tinv,
                             out=(s.ens_raw_sub, s.ens_preds_sub, s.ens_rule))
 
-    def _pseudo_chunk(self, imgs, tinv, thr, rule, want_hm):
+    def _pseudo_chunk(self, imgs, tinv, thr, rule, want_hm, dist_thr=None):
         N, R = imgs.shape[0], imgs.shape[2]
-        s, new = self._slot(N, R, True, pseudo=True)
+        s, new = self._slot(N, R, True, pseudo=True, have_tinv=tinv is not None)
         s.imgs.copy_(imgs, non_blocking=True)
         if tinv is not None:
             s.tinv.copy_(tinv, non_blocking=True)
         s.thr.fill_(thr)                                            # read by the kernel at replay
+        if s.unc:
+            s.dist_thr.fill_(0.0 if dist_thr is None else dist_thr)  # likewise
         self._launch(s, new, self._run_pseudo)
         have = tinv is not None
         select = s.select > 0
-        selected = select.all(0) if rule == "unanimous" else s.ens_score >= s.thr
+        if rule == "uncertainty":
+            selected = (s.unc_select > 0).all(0)
+        else:
+            selected = select.all(0) if rule == "unanimous" else s.ens_score >= s.thr
         out = {"raw": s.raw.clone(), "scores": s.scores.clone(),
                "preds": s.preds.clone() if have else None,
                "preds_mean": s.mean.clone() if have else None,
@@ -430,16 +533,26 @@ class Predictor:
             out.update({"ens_raw_sub": s.ens_raw_sub.clone(), "ens_preds_sub": s.ens_preds_sub.clone() if have else None,
                         "ens_refine_rule": s.ens_rule.clone(),
                         "kps_sub": assemble_kps(s.ens_preds_sub, selected) if have else None})
+        if s.unc:
+            out.update(self._unc_keys(s))
+            if dist_thr is not None:
+                out["unc_select"] = s.unc_select > 0
         if want_hm:
             out["heatmaps"] = s.heatmaps.clone()
             out["mean_heatmap"] = s.mean_hm.clone()
         return out
 
     _PER_MEMBER = ("raw", "scores", "preds", "member_select", "disagree", "heatmaps", "raw_sub", "preds_sub",
-                   "refine_rule")
+                   "refine_rule", "view_legal", "int_dist", "aug_coord", "mix_dist", "unc", "unc_select")
+    _PER_SAMPLE_UNC = ("ext_dist", "aext_dist", "ext_views")
+    _PER_VIEW = ("view_preds", "view_scores")                       # [M,V,N,...]
+
+    def _cat_axis(self, key, per_sample):
+        """The sample axis of a result key: chunks are concatenated along it."""
+        return 2 if key in self._PER_VIEW else 0 if key in per_sample else 1
 
     def pseudo_label(self, imgs, center=None, scale=None, thr=0.95, rule="unanimous", return_heatmaps=False,
-                     out_res=None):
+                     out_res=None, dist_thr=None):
         """The UBPL ensemble pseudo-labels of imgs (JointPseudoLoss3's target and mask,
         utils/losses.py:176-210, with every network in the student's place in turn): which
         joints do the networks agree on confidently enough to use as labels?  Same inputs,
@@ -452,15 +565,23 @@ class Predictor:
           disagree [M,N,K]                   mean_px (p_m - T)^2 (:184);
           selected [N,K] bool                rule "unanimous": every member selects;
                                              rule "ensemble": ens_score >= thr alone;
+                                             rule "uncertainty": unc_select of every member;
           spread [N,K]                       max over m of |raw[m] - ens_raw|, heatmap pixels;
           kps [N,K,3]                        (ens_preds x, y, selected as 0/1), the meta["kpsMap"]
                                              layout (None without center / scale);
         with refine on, predict's sub-pixel keys and ens_raw_sub [N,K,2], ens_preds_sub [N,K,2],
         ens_refine_rule [N,K] (the refinement of the ensemble peak on T) and kps_sub [N,K,3]
         (ens_preds_sub x, y, selected); spread stays on the integer peaks;
-        with return_heatmaps, heatmaps [M,N,K,H,W] and mean_heatmap [N,K,H,W] (T).
-        thr defaults to the reference's pseudoScoreThr; one captured graph serves every thr."""
+        with return_heatmaps, heatmaps [M,N,K,H,W] and mean_heatmap [N,K,H,W] (T);
+        with uncertainty on, predict's view-consistency keys, and with dist_thr given (required
+        by rule "uncertainty": the reference's args.distThrMax has no default) unc_select [M,N,K]
+        bool: the member is legal, int_dist, ext_dist and aext_dist are each <= dist_thr and
+        mix_dist <= 3 dist_thr (utils/business.py:331-345, :242-247), dist_thr in the units of the
+        distances (image pixels with center / scale, else heatmap cells).
+        thr defaults to the reference's pseudoScoreThr; one captured graph serves every thr and
+        every dist_thr."""
         check_rule(rule)
+        dist_thr = check_dist_thr(rule, dist_thr, self.uncertainty)
         if len(self.models) > 8:
             raise ValueError("ubpl_amd: pseudo_label takes up to 8 networks, got %d" % len(self.models))
         imgs, tinv = self._inputs("pseudo_label", imgs, center, scale, out_res)
@@ -470,13 +591,14 @@ class Predictor:
             for a in range(0, N, self.max_batch):
                 b = min(N, a + self.max_batch)
                 outs.append(self._pseudo_chunk(imgs[a:b], None if tinv is None else tinv[a:b], float(thr), rule,
-                                               bool(return_heatmaps)))
+                                               bool(return_heatmaps), dist_thr))
         if len(outs) == 1:
             return outs[0]
-        return {k: None if outs[0][k] is None else torch.cat([o[k] for o in outs], 1 if k in self._PER_MEMBER else 0)
+        per_sample = [k for k in outs[0] if k not in self._PER_MEMBER]
+        return {k: None if outs[0][k] is None else torch.cat([o[k] for o in outs], self._cat_axis(k, per_sample))
                 for k in outs[0]}
 
-    def label_pool(self, loader, args=None, thr=0.95, rule="unanimous"):
+    def label_pool(self, loader, args=None, thr=0.95, rule="unanimous", dist_thr=None):
         """pseudo_label over a loader of (imgMap, _, meta) batches with meta["center"] /
         meta["scale"] (the shape validate takes; args.outRes, when given, is the resolution of
         the inverse transform).  -> a host dict of plain lists, sample-major: predsArraies
@@ -484,18 +606,24 @@ class Predictor:
         refine on from ens_preds_sub, and the dict records "refine" and "blur_sigma"; with tta
         set it records "tta", the views),
         selected, ens_score, spread [N][K], disagree [N][M][K], thr, rule and
-        selected_fraction [K].  Single process only, as validate."""
+        selected_fraction [K].  With uncertainty on it also records int_dist, unc [N][M][K],
+        ext_dist, aext_dist [N][K] and dist_thr (None when not given), in image pixels.  Single
+        process only, as validate."""
         from . import dist as D
         if D.is_dist():
             raise NotImplementedError("ubpl_amd: Predictor.label_pool runs in one process")
         check_rule(rule)
+        dist_thr = check_dist_thr(rule, dist_thr, self.uncertainty)
         on = self.refine != "none"
         keys = ("ens_preds_sub" if on else "ens_preds", "selected", "ens_score", "spread", "disagree")
+        if self.uncertainty:
+            keys += ("int_dist", "unc", "ext_dist", "aext_dist")
         cols = {k: [] for k in keys}
         for imgMap, _, meta in loader:
             out = self.pseudo_label(imgMap.float(), meta["center"], meta["scale"], thr=thr, rule=rule,
-                                    out_res=None if args is None else args.outRes)
-            out["disagree"] = out["disagree"].transpose(0, 1)
+                                    out_res=None if args is None else args.outRes, dist_thr=dist_thr)
+            for k in ("disagree",) + (("int_dist", "unc") if self.uncertainty else ()):   # [M,N,K] -> sample-major
+                out[k] = out[k].transpose(0, 1)
             for k in keys:
                 cols[k].append(out[k].cpu())
         cat = {k: torch.cat(v) if v else torch.zeros(0) for k, v in cols.items()}
@@ -508,6 +636,9 @@ class Predictor:
             d.update({"refine": self.refine, "blur_sigma": self.blur_sigma})
         if self.tta is not None:
             d["tta"] = [list(v) for v in self.tta]
+        if self.uncertainty:
+            d.update({k: cat[k].tolist() for k in ("int_dist", "unc", "ext_dist", "aext_dist")})
+            d["dist_thr"] = dist_thr
         return d
 
     def validate(self, loader, args):
