@@ -179,7 +179,8 @@ def test_chunks_concatenate_on_the_right_axes():
     for name, kwargs in (("predict", {}), ("pseudo_label", {"rule": "uncertainty", "dist_thr": 6.0, "thr": 0.1})):
         out = getattr(chunked, name)(x, center, scale, **kwargs)
         parts = [getattr(whole, name)(x[a:b], center[a:b], scale[a:b], **kwargs) for a, b in ((0, 2), (2, 4), (4, 5))]
-        per_member = Predictor._PER_MEMBER
+        per_member = ("raw", "scores", "preds", "member_select", "disagree", "heatmaps", "raw_sub", "preds_sub",
+                      "refine_rule", "view_legal", "int_dist", "aug_coord", "mix_dist", "unc", "unc_select")
         for key in out:
             ax = axis.get(key, 1 if key in per_member else 0)
             assert _eq(out[key], torch.cat([p[key] for p in parts], ax)), (name, key)

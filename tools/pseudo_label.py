@@ -92,7 +92,7 @@ def main():
 
     from ubpl_amd import Predictor, _lib, checkpoint, mouse
     from ubpl_amd.hourglass import pose_model
-    from ubpl_amd.predict import DEFAULT_BLUR_SIGMA, check_rule
+    from ubpl_amd.predict_args import DEFAULT_BLUR_SIGMA, check_rule, view_count
     rules = []                                   # (rule, dist_thr or None), one labelling each
     for rule in a.rule.split(","):
         if check_rule(rule) != "uncertainty":
@@ -133,7 +133,7 @@ def main():
     vargs = types.SimpleNamespace(outRes=data.outRes, pck_ref=data.pck_ref, pck_thr=data.pck_thr)
     rows = []
     if unc:                                      # view consistency needs views to compare
-        rows_of_views = [t for t in rows_of_views if t[1] is not None and len(t[1]) * (2 if t[2] else 1) >= 2]
+        rows_of_views = [t for t in rows_of_views if view_count(t[1], t[2]) >= 2]
     several = len(variants) * len(rows_of_views) * len(rules) > 1
     for refine, sg, (row_name, views, flip), (rule, dist_thr) in [(r, g, t, u) for r, g in variants
                                                                   for t in rows_of_views for u in rules]:
@@ -144,7 +144,7 @@ def main():
                        "split": "Mouse_100_500_0.3 valid", "images": len(d["predsArraies"]), "trained": trained}
         out = a.out if not several else "%s.%s%s%s%s.json" % (
             os.path.splitext(a.out)[0], refine, "_s%g" % sg if refine == "taylor" else "",
-            "" if len(rows_of_views) == 1 else ".v%d" % (P.views or (2 if flip else 1)),
+            "" if len(rows_of_views) == 1 else ".v%d" % P.passes,
             "" if len(rules) == 1 else ".%s%s" % (rule, "" if dist_thr is None else "_%g" % dist_thr))
         checkpoint.save_pseudo_data(d, out)
         preds = torch.tensor(d["predsArraies"])
@@ -155,7 +155,7 @@ def main():
         P.release()
         rows.append({"out": out, "refine": refine, "blur_sigma": sg if refine == "taylor" else None,
                      "views": row_name, "tta": views, "flip_test": flip,
-                     "forward_passes_per_image": P.views or (2 if flip else 1),
+                     "forward_passes_per_image": P.passes,
                      "images": len(preds), "thr": a.thr, "rule": rule, "dist_thr": dist_thr,
                      "selected_fraction": round(float(sel.float().mean()), 4),
                      "selected_fraction_per_joint": [round(v, 4) for v in d["selected_fraction"]],

@@ -173,6 +173,42 @@ def flip_perm(K, pairs):
     return torch.tensor(perm, dtype=torch.int32)
 
 
+def _chk_maps(t, name, counts, strides, plane, signed=True):
+    """t (None: nothing to check) holds strided maps: counts[i] steps of strides[i] floats, then
+    one block of `plane` floats.  signed=False: a negative stride is refused as well."""
+    if t is None:
+        return
+    _chk(t, name)
+    need = sum((n - 1) * st for n, st in zip(counts, strides)) + plane
+    if t.numel() < need or not (signed or min(strides) >= 0):
+        if len(counts) == 1:
+            raise ValueError("ubpl_amd: %s holds %d floats, %d maps of stride %d need %d"
+                             % (name, t.numel(), counts[0], strides[0], need))
+        raise ValueError("ubpl_amd: %s holds %d floats, %d x %d maps of strides %d, %d need %d"
+                         % (name, t.numel(), *counts, *strides, need))
+
+
+def _chk_entries(perm, K, tinv, swap=None, V=None, N=None):
+    """perm int32 [K], swap int32 [V] and tinv float64 ([N,6] where N is given), each or None."""
+    _chk(swap, "swap", torch.int32)
+    _chk(perm, "perm", torch.int32)
+    _chk(tinv, "tinv", torch.float64)
+    if swap is not None and swap.numel() != V:
+        raise ValueError("ubpl_amd: swap has %d entries for %d views" % (swap.numel(), V))
+    if perm is not None and perm.numel() != K:
+        raise ValueError("ubpl_amd: perm has %d entries for %d joints" % (perm.numel(), K))
+    if N is not None and tinv is not None and tinv.numel() != N * 6:
+        raise ValueError("ubpl_amd: tinv has %d entries for %d samples" % (tinv.numel(), N))
+
+
+def _outs(out, dev, *rows):
+    """The outputs of a wrapper: `out` as given, or per (shape, wanted) row a fresh float32 tensor
+    or None."""
+    if out is not None:
+        return tuple(out)
+    return tuple(torch.empty(shape, device=dev, dtype=F32) if wanted else None for shape, wanted in rows)
+
+
 def decode_heatmaps_flip(hm, hm_flip, sb, N, K, H, W, perm=None, tinv=None, want_merged=False, out=None):
     """Flip-test decode (ubpl_decode_heatmaps_flip): hm / hm_flip are tensors whose
     first element is map (0, 0) — views at an element offset, e.g. the last stack of
@@ -180,25 +216,11 @@ def decode_heatmaps_flip(hm, hm_flip, sb, N, K, H, W, perm=None, tinv=None, want
     strided decode.  perm: device int32 [K] (flip_perm(...).to(device)) or None.
     -> (raw [N,K,2], preds [N,K,2] or None, scores [N,K], merged [N,K,H,W] or None);
     out = (raw, preds, scores, merged): write into these instead of allocating."""
-    for t, nm in ((hm, "hm"), (hm_flip, "hm_flip")):
-        if t is None:
-            continue
-        _chk(t, nm)
-        if t.numel() < (N - 1) * sb + K * H * W:
-            raise ValueError("ubpl_amd: %s holds %d floats, %d maps of stride %d need %d"
-                             % (nm, t.numel(), N, sb, (N - 1) * sb + K * H * W))
-    _chk(perm, "perm", torch.int32)
-    _chk(tinv, "tinv", torch.float64)
-    if perm is not None and perm.numel() != K:
-        raise ValueError("ubpl_amd: perm has %d entries for %d joints" % (perm.numel(), K))
-    dev = hm.device
-    if out is not None:
-        raw, preds, scores, merged = out
-    else:
-        raw = torch.empty((N, K, 2), device=dev, dtype=F32)
-        preds = torch.empty((N, K, 2), device=dev, dtype=F32) if tinv is not None else None
-        scores = torch.empty((N, K), device=dev, dtype=F32)
-        merged = torch.empty((N, K, H, W), device=dev, dtype=F32) if want_merged else None
+    _chk_maps(hm, "hm", (N,), (sb,), K * H * W)
+    _chk_maps(hm_flip, "hm_flip", (N,), (sb,), K * H * W)
+    _chk_entries(perm, K, tinv)
+    raw, preds, scores, merged = _outs(out, hm.device, ((N, K, 2), True), ((N, K, 2), tinv is not None),
+                                       ((N, K), True), ((N, K, H, W), want_merged))
     call("ubpl_decode_heatmaps_flip", hm, hm_flip, int(sb), N, K, H, W, perm, tinv, merged, raw, preds, scores)
     return raw, preds, scores, merged
 
@@ -214,26 +236,14 @@ def ensemble_pseudo(hm, sm, sb, M, N, K, H, W, thr, tinv=None, want_mean=False, 
     out = the same tuple: write into these instead of allocating (select is required)."""
     if not 1 <= M <= 8:
         raise ValueError("ubpl_amd: ensemble_pseudo takes 1 to 8 members, got %d" % M)
-    _chk(hm, "hm")
-    need = (M - 1) * sm + (N - 1) * sb + K * H * W
-    if hm.numel() < need:
-        raise ValueError("ubpl_amd: hm holds %d floats, %d x %d maps of strides %d, %d need %d"
-                         % (hm.numel(), M, N, sm, sb, need))
+    _chk_maps(hm, "hm", (M, N), (sm, sb), K * H * W)
     _chk(thr, "thr")
     _chk(tinv, "tinv", torch.float64)
     if thr is None or thr.numel() != 1:
         raise ValueError("ubpl_amd: thr is a device float32 tensor of one element")
-    dev = hm.device
-    if out is not None:
-        ens_raw, ens_preds, ens_score, member_score, disagree, select, mean_hm = out
-    else:
-        ens_raw = torch.empty((N, K, 2), device=dev, dtype=F32)
-        ens_preds = torch.empty((N, K, 2), device=dev, dtype=F32) if tinv is not None else None
-        ens_score = torch.empty((N, K), device=dev, dtype=F32)
-        member_score = torch.empty((M, N, K), device=dev, dtype=F32)
-        disagree = torch.empty((M, N, K), device=dev, dtype=F32)
-        select = torch.empty((M, N, K), device=dev, dtype=F32)
-        mean_hm = torch.empty((N, K, H, W), device=dev, dtype=F32) if want_mean else None
+    ens_raw, ens_preds, ens_score, member_score, disagree, select, mean_hm = _outs(
+        out, hm.device, ((N, K, 2), True), ((N, K, 2), tinv is not None), ((N, K), True), ((M, N, K), True),
+        ((M, N, K), True), ((M, N, K), True), ((N, K, H, W), want_mean))
     if select is None:
         raise ValueError("ubpl_amd: ensemble_pseudo always writes select")
     call("ubpl_ensemble_pseudo", hm, int(sm), int(sb), M, N, K, H, W, tinv, thr, mean_hm, ens_raw, ens_preds, ens_score,
@@ -273,30 +283,16 @@ def refine_peaks(hm, hm_flip, sb, N, K, H, W, perm, raw, mode, taps, tinv=None, 
     mode = REFINE_MODES.get(mode, mode)
     if mode not in (1, 2):
         raise ValueError("ubpl_amd: refine mode is one of %s, got %r" % (", ".join(REFINE_MODES), mode))
-    for t, nm in ((hm, "hm"), (hm_flip, "hm_flip")):
-        if t is None:
-            continue
-        _chk(t, nm)
-        if t.numel() < (N - 1) * sb + K * H * W:
-            raise ValueError("ubpl_amd: %s holds %d floats, %d maps of stride %d need %d"
-                             % (nm, t.numel(), N, sb, (N - 1) * sb + K * H * W))
-    _chk(perm, "perm", torch.int32)
+    _chk_maps(hm, "hm", (N,), (sb,), K * H * W)
+    _chk_maps(hm_flip, "hm_flip", (N,), (sb,), K * H * W)
     _chk(raw, "raw")
     _chk(taps, "taps")
-    _chk(tinv, "tinv", torch.float64)
-    if perm is not None and perm.numel() != K:
-        raise ValueError("ubpl_amd: perm has %d entries for %d joints" % (perm.numel(), K))
+    _chk_entries(perm, K, tinv)
     if raw is None or raw.numel() != N * K * 2:
         raise ValueError("ubpl_amd: raw is the decode's [N,K,2] peaks")
     if taps is None or not 1 <= taps.numel() <= MAX_BLUR_RADIUS + 1:
         raise ValueError("ubpl_amd: taps holds 1 to %d floats (blur_taps)" % (MAX_BLUR_RADIUS + 1))
-    dev = hm.device
-    if out is not None:
-        raw_sub, preds_sub, how = out
-    else:
-        raw_sub = torch.empty((N, K, 2), device=dev, dtype=F32)
-        preds_sub = torch.empty((N, K, 2), device=dev, dtype=F32) if tinv is not None else None
-        how = torch.empty((N, K), device=dev, dtype=F32)
+    raw_sub, preds_sub, how = _outs(out, hm.device, ((N, K, 2), True), ((N, K, 2), tinv is not None), ((N, K), True))
     call("ubpl_refine_peaks", hm, hm_flip, int(sb), N, K, H, W, perm, raw, mode, taps, taps.numel() - 1, tinv,
          raw_sub, preds_sub, how)
     return raw_sub, preds_sub, how
@@ -403,8 +399,7 @@ def warp_views(src, mat, out=None):
         raise ValueError("ubpl_amd: warp_views takes src [N,C,H,W] and mat [V,6]")
     N, C, H, W = src.shape
     V = mat.shape[0]
-    if out is None:
-        out = torch.empty((V, N, C, H, W), device=src.device, dtype=F32)
+    out, = _outs(None if out is None else (out,), src.device, ((V, N, C, H, W), True))
     _chk(out, "out")
     if out.numel() != V * src.numel():
         raise ValueError("ubpl_amd: out holds %d floats, %d views of %d need %d"
@@ -428,29 +423,13 @@ def decode_heatmaps_views(hm, sv, sb, V, N, K, H, W, mat, swap=None, perm=None, 
     out = (raw, preds, scores, merged): write into these instead of allocating."""
     if not 1 <= V <= MAX_VIEWS:
         raise ValueError("ubpl_amd: decode_heatmaps_views takes 1 to %d views, got %d" % (MAX_VIEWS, V))
-    _chk(hm, "hm")
-    need = (V - 1) * sv + (N - 1) * sb + K * H * W
-    if sv < 0 or sb < 0 or hm.numel() < need:
-        raise ValueError("ubpl_amd: hm holds %d floats, %d x %d maps of strides %d, %d need %d"
-                         % (hm.numel(), V, N, sv, sb, need))
+    _chk_maps(hm, "hm", (V, N), (sv, sb), K * H * W, signed=False)
     _chk(mat, "mat")
-    _chk(swap, "swap", torch.int32)
-    _chk(perm, "perm", torch.int32)
-    _chk(tinv, "tinv", torch.float64)
     if mat is None or mat.numel() != V * 6:
         raise ValueError("ubpl_amd: mat is [V,6], one pixel matrix per view")
-    if swap is not None and swap.numel() != V:
-        raise ValueError("ubpl_amd: swap has %d entries for %d views" % (swap.numel(), V))
-    if perm is not None and perm.numel() != K:
-        raise ValueError("ubpl_amd: perm has %d entries for %d joints" % (perm.numel(), K))
-    dev = hm.device
-    if out is not None:
-        raw, preds, scores, merged = out
-    else:
-        raw = torch.empty((N, K, 2), device=dev, dtype=F32)
-        preds = torch.empty((N, K, 2), device=dev, dtype=F32) if tinv is not None else None
-        scores = torch.empty((N, K), device=dev, dtype=F32)
-        merged = torch.empty((N, K, H, W), device=dev, dtype=F32) if want_merged else None
+    _chk_entries(perm, K, tinv, swap, V)
+    raw, preds, scores, merged = _outs(out, hm.device, ((N, K, 2), True), ((N, K, 2), tinv is not None),
+                                       ((N, K), True), ((N, K, H, W), want_merged))
     call("ubpl_decode_heatmaps_views", hm, int(sv), int(sb), V, N, K, H, W, mat, swap, perm, tinv, merged, raw, preds,
          scores)
     return raw, preds, scores, merged
@@ -498,32 +477,20 @@ def view_uncertainty(raw, sm, M, V, N, K, back, dist_thr, swap=None, perm=None, 
                          % (0 if raw is None else raw.numel(), M, sm, V, N, K, need))
     _chk(back, "back")
     _chk(dist_thr, "dist_thr")
-    _chk(swap, "swap", torch.int32)
-    _chk(perm, "perm", torch.int32)
-    _chk(tinv, "tinv", torch.float64)
     if back is None or back.numel() != V * 6:
         raise ValueError("ubpl_amd: back is [V,6], one pixel matrix per view")
     if dist_thr is None or dist_thr.numel() != 1:
         raise ValueError("ubpl_amd: dist_thr is a device float32 tensor of one element")
-    if swap is not None and swap.numel() != V:
-        raise ValueError("ubpl_amd: swap has %d entries for %d views" % (swap.numel(), V))
-    if perm is not None and perm.numel() != K:
-        raise ValueError("ubpl_amd: perm has %d entries for %d joints" % (perm.numel(), K))
-    if tinv is not None and tinv.numel() != N * 6:
-        raise ValueError("ubpl_amd: tinv has %d entries for %d samples" % (tinv.numel(), N))
-    dev = raw.device
-    if out is not None:
-        pts, legal, int_dist, aug_coord, ext_dist, aext_dist, ext_views, mix_dist, unc, select = out
-    else:
-        e = lambda *s: torch.empty(s, device=dev, dtype=F32)
-        pts, legal, int_dist, aug_coord = e(M, V, N, K, 2), e(M, N, K), e(M, N, K), e(M, N, K, 2)
-        ext_dist, aext_dist, ext_views = e(N, K), e(N, K), e(N, K)
-        mix_dist, unc, select = e(M, N, K), e(M, N, K), e(M, N, K)
-    if select is None:
+    _chk_entries(perm, K, tinv, swap, V, N)
+    mnk, nk = (M, N, K), (N, K)                                 # (in UNC_OUTPUTS' order)
+    outs = _outs(out, raw.device, *((shape, True) for shape in ((M, V, N, K, 2), mnk, mnk, (M, N, K, 2), nk, nk, nk,
+                                                                mnk, mnk, mnk)))
+    if len(outs) != len(UNC_OUTPUTS):
+        raise ValueError("ubpl_amd: view_uncertainty writes %d outputs, got %d" % (len(UNC_OUTPUTS), len(outs)))
+    if outs[-1] is None:
         raise ValueError("ubpl_amd: view_uncertainty always writes select")
-    call("ubpl_view_uncertainty", raw, int(sm), M, V, N, K, back, swap, perm, tinv, dist_thr, pts, legal, int_dist,
-         aug_coord, ext_dist, aext_dist, ext_views, mix_dist, unc, select)
-    return pts, legal, int_dist, aug_coord, ext_dist, aext_dist, ext_views, mix_dist, unc, select
+    call("ubpl_view_uncertainty", raw, int(sm), M, V, N, K, back, swap, perm, tinv, dist_thr, *outs)
+    return outs
 
 
 def fliplr(x, out=None):

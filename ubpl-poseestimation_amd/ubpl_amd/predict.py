@@ -51,162 +51,16 @@ uncertainty").  The default False launches and returns exactly what it did witho
 
 There is no CPU fallback.
 """
-import math
 import os
-from collections import OrderedDict
+from functools import partial
 
 import torch
 
 from . import _lib
 from . import kernels as Kn
-
-
-class _Slot:
-    """Static buffers of one (batch size, resolution, heatmaps wanted) and, once
-    captured, the graph that maps its inputs to its outputs."""
-
-    def __init__(self, M, N, K, R, flip, want_hm, dev, refine=False, views=None, unc=None):
-        H = W = R // 4
-        f32 = dict(device=dev, dtype=torch.float32)
-        self.N, self.H, self.W = N, H, W
-        # (views: the view count of Predictor(tta=...), mirrored ones included; view-major rows)
-        self.batch = torch.zeros(((2 * N if flip else N) if views is None else views * N, 3, R, R), **f32)
-        self.imgs = self.batch[:N]
-        self.tinv = torch.zeros((N, 6), device=dev, dtype=torch.float64)
-        self.raw = torch.zeros((M, N, K, 2), **f32)
-        self.preds = torch.zeros((M, N, K, 2), **f32)
-        self.scores = torch.zeros((M, N, K), **f32)
-        self.mean = torch.zeros((N, K, 2), **f32)
-        self.heatmaps = torch.zeros((M, N, K, H, W), **f32) if want_hm else None
-        self.refine = refine
-        if refine:                                  # the sub-pixel decode's outputs (Predictor(refine=...))
-            self.raw_sub = torch.zeros((M, N, K, 2), **f32)
-            self.preds_sub = torch.zeros((M, N, K, 2), **f32)
-            self.rule = torch.zeros((M, N, K), **f32)
-            self.mean_sub = torch.zeros((N, K, 2), **f32)
-        self.unc = unc is not None
-        if self.unc:                                # the per-view peaks and their fold (Predictor(uncertainty=True))
-            V = views
-            self.have_tinv = bool(unc)              # (the kernel's tinv is null or not: part of the slot's key)
-            self.raw_views = torch.zeros((M, V * N, K, 2), **f32)
-            self.scores_views = torch.zeros((M, V * N, K), **f32)
-            if refine:
-                self.raw_views_sub = torch.zeros((M, V * N, K, 2), **f32)
-            self.dist_thr = torch.zeros(1, **f32)
-            self.view_preds = torch.zeros((M, V, N, K, 2), **f32)
-            self.aug_coord = torch.zeros((M, N, K, 2), **f32)
-            for name in ("view_legal", "int_dist", "mix_dist", "unc_value", "unc_select"):
-                setattr(self, name, torch.zeros((M, N, K), **f32))
-            for name in ("ext_dist", "aext_dist", "ext_views"):
-                setattr(self, name, torch.zeros((N, K), **f32))
-        self.graph = None
-
-    def release(self):
-        if self.graph is not None:
-            self.graph.reset()
-            self.graph = None
-
-
-class _PseudoSlot(_Slot):
-    """A slot of pseudo_label: predict's buffers with the merged heatmaps always kept
-    (the ensemble kernel reads them in place), the ensemble outputs and the threshold.
-    One slot serves calls with and without return_heatmaps."""
-
-    def __init__(self, M, N, K, R, flip, dev, refine=False, views=None, unc=None):
-        super().__init__(M, N, K, R, flip, True, dev, refine, views, unc)
-        f32 = dict(device=dev, dtype=torch.float32)
-        self.thr = torch.zeros(1, **f32)
-        self.ens_raw = torch.zeros((N, K, 2), **f32)
-        self.ens_preds = torch.zeros((N, K, 2), **f32)
-        self.ens_score = torch.zeros((N, K), **f32)
-        self.disagree = torch.zeros((M, N, K), **f32)
-        self.select = torch.zeros((M, N, K), **f32)
-        self.spread = torch.zeros((N, K), **f32)
-        self.mean_hm = torch.zeros((N, K, self.H, self.W), **f32)
-        if refine:
-            self.ens_raw_sub = torch.zeros((N, K, 2), **f32)
-            self.ens_preds_sub = torch.zeros((N, K, 2), **f32)
-            self.ens_rule = torch.zeros((N, K), **f32)
-
-
-DEFAULT_BLUR_SIGMA = 1.0
-RULES = ("unanimous", "ensemble", "uncertainty")
-REFINES = ("none", "quarter", "taylor")
-
-
-def check_rule(rule):
-    if rule not in RULES:
-        raise ValueError("ubpl_amd: rule is one of %s, got %r" % (", ".join(RULES), rule))
-    return rule
-
-
-def check_refine(refine, blur_sigma):
-    """The refine / blur_sigma arguments -> (refine, the host taps table or None for "none").
-    The blur belongs to "taylor"; "quarter" reads unblurred values."""
-    if refine not in REFINES:
-        raise ValueError("ubpl_amd: refine is one of %s, got %r" % (", ".join(REFINES), refine))
-    if refine == "none":
-        return refine, None
-    return refine, Kn.blur_taps(blur_sigma if refine == "taylor" else 0.0)
-
-
-def check_tta(tta, flip_test):
-    """The tta / flip_test arguments -> None, or the views as a list of (angle_deg, zoom) floats.
-    The first view is the image itself; with the flip test every view is run mirrored as well."""
-    if tta is None:
-        return None
-    try:
-        views = [(float(a), float(z)) for a, z in tta]
-    except (TypeError, ValueError):
-        raise ValueError("ubpl_amd: tta is a list of (angle_deg, zoom) pairs, got %r" % (tta,))
-    if not views or views[0] != (0.0, 1.0):
-        raise ValueError("ubpl_amd: the first tta view is the image itself, (0, 1)")
-    for a, z in views:
-        if not (math.isfinite(a) and math.isfinite(z)):
-            raise ValueError("ubpl_amd: a tta view is a finite (angle_deg, zoom), got (%r, %r)" % (a, z))
-        if not 0.5 <= z <= 2.0:
-            raise ValueError("ubpl_amd: a tta zoom lies in [0.5, 2], got %r" % z)
-    V = len(views) * (2 if flip_test else 1)
-    if V > Kn.MAX_VIEWS:
-        raise ValueError("ubpl_amd: %d tta views%s make %d, at most %d"
-                         % (len(views), " with their mirrors" if flip_test else "", V, Kn.MAX_VIEWS))
-    return views
-
-
-def check_uncertainty(uncertainty, views, flip_test):
-    """The uncertainty argument against the checked tta views -> bool.  View consistency needs
-    views to compare: tta with at least 2 in all (mirrored ones included)."""
-    if not uncertainty:
-        return False
-    V = 0 if views is None else len(views) * (2 if flip_test else 1)
-    if V < 2:
-        raise ValueError("ubpl_amd: uncertainty=True compares the views of tta: at least 2 in all, got %s"
-                         % ("tta=None" if views is None else "%d" % V))
-    return True
-
-
-def check_dist_thr(rule, dist_thr, uncertainty):
-    """pseudo_label's rule / dist_thr against Predictor(uncertainty=...) -> dist_thr as a float, or
-    None.  The rule "uncertainty" needs both; the reference ships no default threshold
-    (args.distThrMax), and none is invented here."""
-    if rule == "uncertainty" and not uncertainty:
-        raise ValueError('ubpl_amd: rule "uncertainty" needs Predictor(uncertainty=True)')
-    if dist_thr is None:
-        if rule == "uncertainty":
-            raise ValueError('ubpl_amd: rule "uncertainty" needs dist_thr, a distance in the coordinates of the result')
-        return None
-    if not uncertainty:
-        raise ValueError("ubpl_amd: dist_thr needs Predictor(uncertainty=True)")
-    dist_thr = float(dist_thr)
-    if not dist_thr >= 0:
-        raise ValueError("ubpl_amd: dist_thr is a distance >= 0, got %r" % dist_thr)
-    return dist_thr
-
-
-def assemble_kps(ens_preds, selected):
-    """[N,K,2] image coordinates + [N,K] bool -> [N,K,3] (x, y, selected as 0/1), the
-    meta["kpsMap"] layout."""
-    return torch.cat([ens_preds, selected.to(ens_preds.dtype).unsqueeze(-1)], -1)
+from . import predict_slots as PS
+from .predict_args import (DEFAULT_BLUR_SIGMA, REFINES, RULES, assemble_kps, check_dist_thr,  # noqa: F401
+                           check_refine, check_rule, check_tta, check_uncertainty, view_count)
 
 
 class Predictor:
@@ -270,22 +124,26 @@ class Predictor:
         if max_batch < 1 or max_graphs < 1:
             raise ValueError("ubpl_amd: max_batch and max_graphs are at least 1")
         self.flip_test = bool(flip_test)
-        self.perm = None
-        if flip_pairs:
-            self.perm = Kn.flip_perm(self.k, flip_pairs).to(self.device)
+        self.perm = Kn.flip_perm(self.k, flip_pairs).to(self.device) if flip_pairs else None
         self.taps = None if taps is None else taps.to(self.device)
         self.max_batch, self.max_graphs = int(max_batch), int(max_graphs)
-        self.views = None
+        self.views = view_count(self.tta, self.flip_test) or None
         if self.tta is not None:
-            self.views = len(self.tta) * (2 if self.flip_test else 1)
             self.max_batch = min(self.max_batch, max(1, 2 * self.max_batch // self.views))
             self._view_mats = {}                    # resolution -> device (img_mat, hm_mat, swap)
         if self.uncertainty:
             self._back_mats = {}                    # resolution -> device back [V,6] (view cell -> original cell)
         self.use_graph = os.environ.get("UBPL_PREDICT_GRAPH", "1") != "0" if graph is None else bool(graph)
-        self._slots = OrderedDict()
+        self._slots = PS.SlotCache()
+        self._spec = partial(PS.SlotSpec, len(self.models), self.k, self.flip_test, self.views, self.refine != "none",
+                             self.uncertainty)               # + (pseudo, N, R, want_hm, have_tinv) of a call
         self._sets = None
         self.refresh()
+
+    @property
+    def passes(self):
+        """Forward passes per image and network: the views, else 2 with the flip test, else 1."""
+        return self.views or (2 if self.flip_test else 1)
 
     # -- weights ----------------------------------------------------------
     def refresh(self):
@@ -309,39 +167,45 @@ class Predictor:
             torch.cuda.empty_cache()
 
     # -- one batch --------------------------------------------------------
+    def _last_stacks(self, s):
+        """Every network's frozen forward of s.batch in turn -> (mi, the flat output from row 0's
+        last stack on — a view, so the rows' last stacks lie sb floats apart in it —, sb)."""
+        K = self.k
+        for mi, (m, ws) in enumerate(zip(self.models, self._sets)):
+            o = m.forward_frozen(s.batch, ws)                       # [rows, S, K, H, W]
+            S, H, W = o.shape[1], o.shape[3], o.shape[4]
+            if (H, W) != (s.H, s.W):
+                raise RuntimeError("ubpl_amd: heatmaps %dx%d, expected %dx%d" % (H, W, s.H, s.W))
+            yield mi, o.reshape(-1)[(S - 1) * K * H * W:], S * K * H * W
+
+    def _means(self, s):
+        s.mean.copy_(torch.stack(list(s.preds), -1).mean(-1))       # projects/MT_UBPL.py:387
+        if s.refine:
+            s.mean_sub.copy_(torch.stack(list(s.preds_sub), -1).mean(-1))
+
     def _run(self, s):
         """The device work of one batch, on the current stream: static inputs of slot s
         -> its static outputs."""
         if self.tta is not None:
             return self._run_views(s)
-        N, K = s.N, self.k
+        N, K, H, W = s.N, self.k, s.H, s.W
         if self.flip_test:
             Kn.fliplr(s.imgs, out=s.batch[N:])
-        for mi, (m, ws) in enumerate(zip(self.models, self._sets)):
-            o = m.forward_frozen(s.batch, ws)                       # [N or 2N, S, K, H, W]
-            S, H, W = o.shape[1], o.shape[3], o.shape[4]
-            if (H, W) != (s.H, s.W):
-                raise RuntimeError("ubpl_amd: heatmaps %dx%d, expected %dx%d" % (H, W, s.H, s.W))
-            sb, last = S * K * H * W, (S - 1) * K * H * W
-            flat = o.reshape(-1)
-            # the last stack of rows 0..N and N..2N, in place: row stride + base offset
-            hm = flat[last:]
-            hm_flip = flat[N * sb + last:] if self.flip_test else None
+        for mi, hm, sb in self._last_stacks(s):
+            hm_flip = hm[N * sb:] if self.flip_test else None       # rows N..2N, in place
             Kn.decode_heatmaps_flip(hm, hm_flip, sb, N, K, H, W, self.perm, s.tinv,
                                     out=(s.raw[mi], s.preds[mi], s.scores[mi],
-                                         s.heatmaps[mi] if s.heatmaps is not None else None))
+                                         s.heatmaps[mi] if s.spec.want_hm else None))
             if s.refine:
                 Kn.refine_peaks(hm, hm_flip, sb, N, K, H, W, self.perm, s.raw[mi], self.refine, self.taps, s.tinv,
                                 out=(s.raw_sub[mi], s.preds_sub[mi], s.rule[mi]))
-        s.mean.copy_(torch.stack(list(s.preds), -1).mean(-1))       # projects/MT_UBPL.py:387
-        if s.refine:
-            s.mean_sub.copy_(torch.stack(list(s.preds_sub), -1).mean(-1))
+        self._means(s)
 
     def _run_views(self, s):
         """_run with test-time augmentation: the views of s.imgs fill the rest of the view-major
         batch, every network runs once on all of them, and the multi-view decode merges the last
         stacks into s.heatmaps[mi], which the refinement then reads as plain maps."""
-        N, K, V = s.N, self.k, self.views
+        N, K, V, H, W = s.N, self.k, self.views, s.H, s.W
         R = s.batch.shape[2]
         if R not in self._view_mats:
             img_mat, hm_mat, swap = Kn.view_matrices(self.tta, self.flip_test, R, R // 4)
@@ -350,13 +214,8 @@ class Predictor:
         img_mat, hm_mat, swap = self._view_mats[R]
         if V > 1:
             Kn.warp_views(s.imgs, img_mat[1:], out=s.batch[N:])
-        for mi, (m, ws) in enumerate(zip(self.models, self._sets)):
-            o = m.forward_frozen(s.batch, ws)                       # [V*N, S, K, H, W]
-            S, H, W = o.shape[1], o.shape[3], o.shape[4]
-            if (H, W) != (s.H, s.W):
-                raise RuntimeError("ubpl_amd: heatmaps %dx%d, expected %dx%d" % (H, W, s.H, s.W))
-            sb, last = S * K * H * W, (S - 1) * K * H * W
-            Kn.decode_heatmaps_views(o.reshape(-1)[last:], N * sb, sb, V, N, K, H, W, hm_mat, swap, self.perm, s.tinv,
+        for mi, hm_views, sb in self._last_stacks(s):
+            Kn.decode_heatmaps_views(hm_views, N * sb, sb, V, N, K, H, W, hm_mat, swap, self.perm, s.tinv,
                                      out=(s.raw[mi], s.preds[mi], s.scores[mi], s.heatmaps[mi]))
             if s.refine:
                 Kn.refine_peaks(s.heatmaps[mi], None, K * H * W, N, K, H, W, None, s.raw[mi], self.refine, self.taps,
@@ -364,132 +223,20 @@ class Predictor:
             if s.unc:
                 # every view's own peak: the view-major rows share one batch stride, so the last
                 # stacks are a strided plain decode of V*N samples (each view's frame and joint order)
-                hm_views = o.reshape(-1)[last:]
                 Kn.decode_heatmaps_flip(hm_views, None, sb, V * N, K, H, W, None, None,
                                         out=(s.raw_views[mi], None, s.scores_views[mi], None))
                 if s.refine:
                     Kn.refine_peaks(hm_views, None, sb, V * N, K, H, W, None, s.raw_views[mi], self.refine, self.taps,
                                     None, out=(s.raw_views_sub[mi], None, None))
-        s.mean.copy_(torch.stack(list(s.preds), -1).mean(-1))       # projects/MT_UBPL.py:387
-        if s.refine:
-            s.mean_sub.copy_(torch.stack(list(s.preds_sub), -1).mean(-1))
+        self._means(s)
         if s.unc:
             if R not in self._back_mats:
                 self._back_mats[R] = Kn.view_back_matrices(hm_mat).to(self.device)
             Kn.view_uncertainty(s.raw_views_sub if s.refine else s.raw_views, V * N * K * 2, len(self.models), V, N, K,
-                                self._back_mats[R], s.dist_thr, swap, self.perm, s.tinv if s.have_tinv else None,
+                                self._back_mats[R], s.dist_thr, swap, self.perm, s.tinv if s.spec.have_tinv else None,
                                 out=(s.view_preds, s.view_legal, s.int_dist, s.aug_coord, s.ext_dist, s.aext_dist,
                                      s.ext_views, s.mix_dist, s.unc_value, s.unc_select))
 
-    def _slot(self, N, R, want_hm, pseudo=False, have_tinv=False):
-        # (pseudo_label's slots carry a key of their own: predict's graphs and buffers stay its own)
-        want_hm = want_hm or self.tta is not None                   # (the merged maps are the decode's output)
-        key = ("pseudo", N, R) if pseudo else (N, R, want_hm)
-        if self.uncertainty:                                        # (heatmap cells or image coordinates)
-            key = key + (bool(have_tinv),)
-        s = self._slots.get(key)
-        if s is not None:
-            self._slots.move_to_end(key)
-            return s, False
-        while len(self._slots) >= self.max_graphs:
-            _, old = self._slots.popitem(last=False)
-            old.release()
-            del old
-            torch.cuda.empty_cache()
-        a = (len(self.models), N, self.k, R, self.flip_test)
-        on = self.refine != "none"
-        unc = bool(have_tinv) if self.uncertainty else None
-        s = self._slots[key] = (_PseudoSlot(*a, self.device, on, self.views, unc) if pseudo else
-                                _Slot(*a, want_hm, self.device, on, self.views, unc))
-        return s, True
-
-    def _launch(self, s, new, run):
-        """run(s) eagerly, or captured once per slot and replayed."""
-        if not self.use_graph:
-            run(s)
-            return
-        if new:
-            # warm-up: the networks' per-batch-size scratch is allocated here, outside the
-            # graph's pool; then the capture (which records, it does not execute)
-            run(s)
-            torch.cuda.synchronize(self.device)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                run(s)
-            s.graph = g
-        s.graph.replay()
-
-    def _sub_keys(self, s, have):
-        """The sub-pixel entries of a predict / pseudo_label result (refine on)."""
-        return {"raw_sub": s.raw_sub.clone(), "preds_sub": s.preds_sub.clone() if have else None,
-                "preds_mean_sub": s.mean_sub.clone() if have else None, "refine_rule": s.rule.clone()}
-
-    def _unc_keys(self, s):
-        """The view-consistency entries of a predict / pseudo_label result (uncertainty on)."""
-        M, V = len(self.models), self.views
-        scores = s.scores_views.reshape(M, V, s.N, self.k).clone()
-        if self.flip_test and self.perm is not None:                # the mirrored views, in the output joint order
-            scores[:, V // 2:] = scores[:, V // 2:][..., self.perm.long()]
-        return {"view_preds": s.view_preds.clone(), "view_scores": scores, "view_legal": s.view_legal > 0,
-                "int_dist": s.int_dist.clone(), "aug_coord": s.aug_coord.clone(), "ext_dist": s.ext_dist.clone(),
-                "aext_dist": s.aext_dist.clone(), "ext_views": s.ext_views.clone(), "mix_dist": s.mix_dist.clone(),
-                "unc": s.unc_value.clone()}
-
-    def _predict_chunk(self, imgs, tinv, want_hm):
-        N, R = imgs.shape[0], imgs.shape[2]
-        s, new = self._slot(N, R, want_hm, have_tinv=tinv is not None)
-        s.imgs.copy_(imgs, non_blocking=True)
-        if tinv is not None:
-            s.tinv.copy_(tinv, non_blocking=True)
-        self._launch(s, new, self._run)
-        out = {"raw": s.raw.clone(), "scores": s.scores.clone(),
-               "preds": s.preds.clone() if tinv is not None else None,
-               "preds_mean": s.mean.clone() if tinv is not None else None}
-        if s.refine:
-            out.update(self._sub_keys(s, tinv is not None))
-        if s.unc:
-            out.update(self._unc_keys(s))
-        if want_hm:
-            out["heatmaps"] = s.heatmaps.clone()
-        return out
-
-    def _inputs(self, what, imgs, center, scale, out_res):
-        """The argument checks of predict / pseudo_label -> (contiguous images, tinv or None)."""
-        if not torch.is_tensor(imgs) or imgs.dtype != torch.float32 or imgs.dim() != 4 or imgs.shape[1] != 3 \
-                or imgs.shape[2] != imgs.shape[3] or imgs.shape[0] < 1:
-            raise TypeError("ubpl_amd: %s takes float32 images [N,3,R,R], N >= 1" % what)
-        if (center is None) != (scale is None):
-            raise ValueError("ubpl_amd: center and scale come together")
-        N, R = imgs.shape[0], imgs.shape[2]
-        tinv = None
-        if center is not None:
-            from .process import inverse_transforms
-            res = [R // 4, R // 4] if out_res is None else [out_res, out_res]
-            tinv = inverse_transforms(center, scale, res)
-            if tinv.shape[0] != N:
-                raise ValueError("ubpl_amd: %d centers for %d images" % (tinv.shape[0], N))
-        return imgs.contiguous(), tinv
-
-    def predict(self, imgs, center=None, scale=None, return_heatmaps=False, out_res=None):
-        """imgs float32 [N,3,R,R] (host or device) -> dict of device tensors, the caller's own:
-        raw [M,N,K,2] 1-based heatmap coordinates, scores [M,N,K], preds [M,N,K,2] and
-        preds_mean [N,K,2] in image coordinates (None without center / scale), and with
-        return_heatmaps heatmaps [M,N,K,H,W], the (flip- or view-merged) last-stack maps; M networks.
-        out_res: the resolution of the inverse transform (default: the heatmaps')."""
-        imgs, tinv = self._inputs("predict", imgs, center, scale, out_res)
-        N = imgs.shape[0]
-        outs = []
-        with torch.cuda.device(self.device), torch.no_grad():
-            for a in range(0, N, self.max_batch):
-                b = min(N, a + self.max_batch)
-                outs.append(self._predict_chunk(imgs[a:b], None if tinv is None else tinv[a:b], bool(return_heatmaps)))
-        if len(outs) == 1:
-            return outs[0]
-        per_sample = ("preds_mean", "preds_mean_sub") + self._PER_SAMPLE_UNC
-        return {k: None if outs[0][k] is None else torch.cat([o[k] for o in outs], self._cat_axis(k, per_sample))
-                for k in outs[0]}
-
-    # -- ensemble pseudo-labels --------------------------------------------
     def _run_pseudo(self, s):
         """_run, then the ensemble kernel on the merged heatmaps it left in s.heatmaps
         (the members' peaks are s.scores already: not written again) and the members'
@@ -505,52 +252,52 @@ class Predictor:
             Kn.refine_peaks(s.mean_hm, None, K * H * W, N, K, H, W, None, s.ens_raw, self.refine, self.taps, s.tinv,
                             out=(s.ens_raw_sub, s.ens_preds_sub, s.ens_rule))
 
-    def _pseudo_chunk(self, imgs, tinv, thr, rule, want_hm, dist_thr=None):
-        N, R = imgs.shape[0], imgs.shape[2]
-        s, new = self._slot(N, R, True, pseudo=True, have_tinv=tinv is not None)
+    # -- one call ---------------------------------------------------------
+    def _chunk(self, imgs, tinv, pseudo, want_hm, thr=None, dist_thr=None, rule=None):
+        """One chunk through its slot: static inputs filled, launched, the result cloned out.
+        (pseudo_label's slots are their own: predict's graphs and buffers stay its own.)"""
+        spec = self._spec(pseudo, imgs.shape[0], imgs.shape[2], want_hm, tinv is not None)
+        s, new = self._slots.fetch(spec, self.max_graphs, self.device)
         s.imgs.copy_(imgs, non_blocking=True)
         if tinv is not None:
             s.tinv.copy_(tinv, non_blocking=True)
-        s.thr.fill_(thr)                                            # read by the kernel at replay
-        if s.unc:
-            s.dist_thr.fill_(0.0 if dist_thr is None else dist_thr)  # likewise
-        self._launch(s, new, self._run_pseudo)
-        have = tinv is not None
-        select = s.select > 0
-        if rule == "uncertainty":
-            selected = (s.unc_select > 0).all(0)
-        else:
-            selected = select.all(0) if rule == "unanimous" else s.ens_score >= s.thr
-        out = {"raw": s.raw.clone(), "scores": s.scores.clone(),
-               "preds": s.preds.clone() if have else None,
-               "preds_mean": s.mean.clone() if have else None,
-               "ens_raw": s.ens_raw.clone(), "ens_preds": s.ens_preds.clone() if have else None,
-               "ens_score": s.ens_score.clone(), "member_select": select, "disagree": s.disagree.clone(),
-               "selected": selected, "spread": s.spread.clone(),
-               "kps": assemble_kps(s.ens_preds, selected) if have else None}
-        if s.refine:
-            out.update(self._sub_keys(s, have))
-            out.update({"ens_raw_sub": s.ens_raw_sub.clone(), "ens_preds_sub": s.ens_preds_sub.clone() if have else None,
-                        "ens_refine_rule": s.ens_rule.clone(),
-                        "kps_sub": assemble_kps(s.ens_preds_sub, selected) if have else None})
-        if s.unc:
-            out.update(self._unc_keys(s))
-            if dist_thr is not None:
-                out["unc_select"] = s.unc_select > 0
-        if want_hm:
-            out["heatmaps"] = s.heatmaps.clone()
-            out["mean_heatmap"] = s.mean_hm.clone()
-        return out
+        if pseudo:                                                  # read by the kernels at replay
+            s.thr.fill_(thr)
+            if s.unc:
+                s.dist_thr.fill_(0.0 if dist_thr is None else dist_thr)
+        PS.launch(s, new, self._run_pseudo if pseudo else self._run, self.use_graph)
+        return PS.result(s, PS.Ask(tinv is not None, want_hm, dist_thr, rule, self.perm))
 
-    _PER_MEMBER = ("raw", "scores", "preds", "member_select", "disagree", "heatmaps", "raw_sub", "preds_sub",
-                   "refine_rule", "view_legal", "int_dist", "aug_coord", "mix_dist", "unc", "unc_select")
-    _PER_SAMPLE_UNC = ("ext_dist", "aext_dist", "ext_views")
-    _PER_VIEW = ("view_preds", "view_scores")                       # [M,V,N,...]
+    def _chunked(self, what, imgs, center, scale, out_res, **chunk_kw):
+        """The argument checks of predict / pseudo_label, then _chunk over at most max_batch images
+        at a time, and the chunks' results as one."""
+        if not torch.is_tensor(imgs) or imgs.dtype != torch.float32 or imgs.dim() != 4 or imgs.shape[1] != 3 \
+                or imgs.shape[2] != imgs.shape[3] or imgs.shape[0] < 1:
+            raise TypeError("ubpl_amd: %s takes float32 images [N,3,R,R], N >= 1" % what)
+        if (center is None) != (scale is None):
+            raise ValueError("ubpl_amd: center and scale come together")
+        N, R = imgs.shape[0], imgs.shape[2]
+        tinv = None
+        if center is not None:
+            from .process import inverse_transforms
+            res = [R // 4, R // 4] if out_res is None else [out_res, out_res]
+            tinv = inverse_transforms(center, scale, res)
+            if tinv.shape[0] != N:
+                raise ValueError("ubpl_amd: %d centers for %d images" % (tinv.shape[0], N))
+        imgs, B = imgs.contiguous(), self.max_batch
+        with torch.cuda.device(self.device), torch.no_grad():
+            return PS.concat([self._chunk(imgs[a:a + B], None if tinv is None else tinv[a:a + B], **chunk_kw)
+                              for a in range(0, N, B)])
 
-    def _cat_axis(self, key, per_sample):
-        """The sample axis of a result key: chunks are concatenated along it."""
-        return 2 if key in self._PER_VIEW else 0 if key in per_sample else 1
+    def predict(self, imgs, center=None, scale=None, return_heatmaps=False, out_res=None):
+        """imgs float32 [N,3,R,R] (host or device) -> dict of device tensors, the caller's own:
+        raw [M,N,K,2] 1-based heatmap coordinates, scores [M,N,K], preds [M,N,K,2] and
+        preds_mean [N,K,2] in image coordinates (None without center / scale), and with
+        return_heatmaps heatmaps [M,N,K,H,W], the (flip- or view-merged) last-stack maps; M networks.
+        out_res: the resolution of the inverse transform (default: the heatmaps')."""
+        return self._chunked("predict", imgs, center, scale, out_res, pseudo=False, want_hm=bool(return_heatmaps))
 
+    # -- ensemble pseudo-labels --------------------------------------------
     def pseudo_label(self, imgs, center=None, scale=None, thr=0.95, rule="unanimous", return_heatmaps=False,
                      out_res=None, dist_thr=None):
         """The UBPL ensemble pseudo-labels of imgs (JointPseudoLoss3's target and mask,
@@ -584,19 +331,8 @@ class Predictor:
         dist_thr = check_dist_thr(rule, dist_thr, self.uncertainty)
         if len(self.models) > 8:
             raise ValueError("ubpl_amd: pseudo_label takes up to 8 networks, got %d" % len(self.models))
-        imgs, tinv = self._inputs("pseudo_label", imgs, center, scale, out_res)
-        N = imgs.shape[0]
-        outs = []
-        with torch.cuda.device(self.device), torch.no_grad():
-            for a in range(0, N, self.max_batch):
-                b = min(N, a + self.max_batch)
-                outs.append(self._pseudo_chunk(imgs[a:b], None if tinv is None else tinv[a:b], float(thr), rule,
-                                               bool(return_heatmaps), dist_thr))
-        if len(outs) == 1:
-            return outs[0]
-        per_sample = [k for k in outs[0] if k not in self._PER_MEMBER]
-        return {k: None if outs[0][k] is None else torch.cat([o[k] for o in outs], self._cat_axis(k, per_sample))
-                for k in outs[0]}
+        return self._chunked("pseudo_label", imgs, center, scale, out_res, pseudo=True,
+                             want_hm=bool(return_heatmaps), thr=float(thr), dist_thr=dist_thr, rule=rule)
 
     def label_pool(self, loader, args=None, thr=0.95, rule="unanimous", dist_thr=None):
         """pseudo_label over a loader of (imgMap, _, meta) batches with meta["center"] /
@@ -615,17 +351,14 @@ class Predictor:
         check_rule(rule)
         dist_thr = check_dist_thr(rule, dist_thr, self.uncertainty)
         on = self.refine != "none"
-        keys = ("ens_preds_sub" if on else "ens_preds", "selected", "ens_score", "spread", "disagree")
-        if self.uncertainty:
-            keys += ("int_dist", "unc", "ext_dist", "aext_dist")
+        unc_keys = ("int_dist", "unc", "ext_dist", "aext_dist") if self.uncertainty else ()
+        keys = ("ens_preds_sub" if on else "ens_preds", "selected", "ens_score", "spread", "disagree") + unc_keys
         cols = {k: [] for k in keys}
         for imgMap, _, meta in loader:
             out = self.pseudo_label(imgMap.float(), meta["center"], meta["scale"], thr=thr, rule=rule,
                                     out_res=None if args is None else args.outRes, dist_thr=dist_thr)
-            for k in ("disagree",) + (("int_dist", "unc") if self.uncertainty else ()):   # [M,N,K] -> sample-major
-                out[k] = out[k].transpose(0, 1)
-            for k in keys:
-                cols[k].append(out[k].cpu())
+            for k in keys:                                          # ([M,N,K] -> sample-major)
+                cols[k].append((out[k].transpose(0, 1) if PS.AXIS[k] == 1 else out[k]).cpu())
         cat = {k: torch.cat(v) if v else torch.zeros(0) for k, v in cols.items()}
         sel = cat["selected"]
         d = {"predsArraies": cat[keys[0]].tolist(), "selected": sel.tolist(),
@@ -637,7 +370,7 @@ class Predictor:
         if self.tta is not None:
             d["tta"] = [list(v) for v in self.tta]
         if self.uncertainty:
-            d.update({k: cat[k].tolist() for k in ("int_dist", "unc", "ext_dist", "aext_dist")})
+            d.update({k: cat[k].tolist() for k in unc_keys})
             d["dist_thr"] = dist_thr
         return d
 
