@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from f16_split_ref import fp16_wscale as _fp16_wscale
 from guard_ref import guard_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -89,14 +90,6 @@ def test_header_declares_guard_entries():
     src = _abi.gen(_abi.parse(open(HEADER).read()))
     assert 'm.def("grad_guard_scratch(int n) -> int");' in src
     assert "Tensor? guard, Tensor(a5!)? skipped) -> ()" in src
-
-
-def _fp16_wscale(K):
-    """csrc/common.h fp16_wscale: 2^(9 + ceil(log2 sqrt K))."""
-    e = 0
-    while (1 << (2 * e)) < K:
-        e += 1
-    return float(1 << (9 + e))
 
 
 def test_fp16_overflow_plant_arithmetic():
