@@ -58,7 +58,11 @@ int ubpl_heatmap_row_stats(const float* a, int64_t a_sb, int64_t a_ss, const flo
                            int64_t t_sm, int M, int B, int S, int K, int HW, float* sq_mean, float* amax,
                            float* tmax, void* stream);
 /* Loss reduction + counts on device.  kind 0 MSE/consistency, 1 teacher-
- * confidence mask (mt2), 2 UBPL pseudo mask.  out_sum[1] f32; out_cnt[4] int32 =
+ * confidence mask (mt2), 2 UBPL pseudo mask, 3 UBPL pseudo mask with a given
+ * selection: kind 2 in everything (l *= sw, the counts, out_score, out_w) but the
+ * row mask, (gate[b*K+k] > 0) * (amax >= thr) * (tmax >= thr) — with thr = -inf
+ * the selection alone decides (a NaN score still never selects); gate [B,K] is
+ * required (hipErrorInvalidValue without).  out_sum[1] f32; out_cnt[4] int32 =
  * {nStack*#gate>0, n_pseudo, n_sel, #rows sw>0}; out_score[K] (kinds 1,2);
  * out_w[B*S*K] per-row weight for the backward. */
 /*@ sq_mean:f32[B*S*K] amax:f32[B*S*K] tmax:f32[B*S*K] gate:f32[B*K] sw:f32[B] out_sum:f32[1] out_cnt:i32[4] out_score:f32[K] out_w:f32[B*S*K] */
@@ -264,6 +268,34 @@ int ubpl_view_uncertainty(const float* raw, int64_t sm, int M, int V, int N, int
                           const int* swap, const int* perm, const double* tinv, const float* dist_thr, float* pts,
                           float* legal, float* int_dist, float* aug_coord, float* ext_dist, float* aext_dist,
                           float* ext_views, float* mix_dist, float* unc, float* select, void* stream);
+/* The same rule where every (view, sample) has its own matrix: the training
+ * step's two augmented views, each with its own random flip, scale and
+ * rotation (the setting utils/business.py pseudo_cal_unc was written for).  It
+ * shares ubpl_view_uncertainty's device code and differs in four things:
+ *   back [V][N][6] f32: point (m, v, n, k) is mapped by back + (v*N + n)*6;
+ *   raw has a member stride sm and a view stride sv, in floats: the point is the
+ *   pair at raw + m*sm + v*sv + (n*K + k)*2, so a [V][M][N][K][2] buffer (sm =
+ *   N*K*2, sv = M*N*K*2) is filled by one decode launch per view, and
+ *   ubpl_view_uncertainty's view-major member blocks are sm = V*N*K*2, sv =
+ *   N*K*2.  sv >= N*K*2; with M > 1, sm >= N*K*2 and the blocks nest one way or
+ *   the other: sm >= (V-1)*sv + N*K*2 or sv >= (M-1)*sm + N*K*2
+ *   (hipErrorInvalidValue otherwise);
+ *   no swap / perm (the reference's training flip, kps_fliplr, mirrors x and
+ *   swaps no joints) and no tinv: p = (ox + 1, oy + 1), in whatever frame back
+ *   maps to (kernels.train_back_matrices: source-image pixels), legal iff raw is
+ *   not (0,0) and p is finite;
+ *   gate [N,K] (nullable) = 1 iff select is 1 for every member m < M, else 0:
+ *   the unc_select.all(0) of Predictor.pseudo_label(rule="uncertainty").
+ * Everything else — legality, the 999 sentinel, int_dist, aug_coord, ext_dist,
+ * aext_dist, ext_views, mix_dist, unc, select, the sequential f32 sums without
+ * FMA, dist_thr read from the device, 1 <= M <= 8, 2 <= V <= 16, no atomics — is
+ * the rule above, word for word.  Every output but select is nullable. */
+/*@ raw:f32[(M-1)*sm+(V-1)*sv+(int64_t)N*K*2] back:f32[(int64_t)V*N*6] dist_thr:f32[1] pts:f32[(int64_t)M*V*N*K*2] legal:f32[(int64_t)M*N*K] int_dist:f32[(int64_t)M*N*K] aug_coord:f32[(int64_t)M*N*K*2] ext_dist:f32[N*K] aext_dist:f32[N*K] ext_views:f32[N*K] mix_dist:f32[(int64_t)M*N*K] unc:f32[(int64_t)M*N*K] select:f32[(int64_t)M*N*K] gate:f32[N*K] */
+int ubpl_view_uncertainty_samples(const float* raw, int64_t sm, int64_t sv, int M, int V, int N, int K,
+                                  const float* back, const float* dist_thr, float* pts, float* legal,
+                                  float* int_dist, float* aug_coord, float* ext_dist, float* aext_dist,
+                                  float* ext_views, float* mix_dist, float* unc, float* select, float* gate,
+                                  void* stream);
 /* EvaluationUtils.acc_pck (utils/evaluation.py:91-139).  errs/accs [K+1];
  * hits/valid [K] int32 (nullable) for cross-rank aggregation. */
 /*@ preds:f32[N*K*2] gts:f32[N*K*3] errs:f32[K+1] accs:f32[K+1] hits:i32[K] valid:i32[K] */

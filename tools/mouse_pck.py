@@ -8,6 +8,11 @@ the fused train step, HIP decode + PCK.
 
     python tools/mouse_pck.py [--epochs 100] [--model HG2] [--out profiles/r02_mouse_pck.json]
 
+--pseudo-rule uncertainty / score+uncertainty (with --dist-thr, source-image pixels) selects the
+pseudo labels by the view-consistency rule of the training step; the loader then
+hands the views' matrices on as meta["viewmat"].  Every run logs the share of pseudo labels its
+rule selected per epoch ("sel_rate").
+
 Reads tests/golden/mouse_100_500_0.3/ (tools/pack_mouse.py).
 """
 import argparse
@@ -35,6 +40,10 @@ def parser():
     ap.add_argument("--valid-every", type=int, default=5)
     ap.add_argument("--no-aug", action="store_true")
     ap.add_argument("--seed", type=int, default=1388)
+    ap.add_argument("--pseudo-rule", default="score", choices=["score", "uncertainty", "score+uncertainty"])
+    ap.add_argument("--dist-thr", type=float, default=None, help="distThrMax, source-image pixels")
+    ap.add_argument("--pseudo-refine", default=None, choices=["none", "quarter", "taylor"])
+    ap.add_argument("--pseudo-blur-sigma", type=float, default=None)
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "mouse_pck.json"))
     return ap
 
@@ -42,7 +51,7 @@ def parser():
 def main():
     log = run(parser().parse_args())
     print(json.dumps({"best_pck": log["best_pck"], "best_epoch": log["best_epoch"], "final_pck": log["final_pck"],
-                      "wall_s": log["wall_s"]}))
+                      "sel_rate_last10": log["sel_rate_last10"], "wall_s": log["wall_s"]}))
 
 
 def run(a, write=True, keep=None):
@@ -71,6 +80,13 @@ def run(a, write=True, keep=None):
         FDLWeight_rampup=100, pseudoWeight_max=1.0, pseudoWeight_min=1.0, pseudoWeight_rampup=100,
         FDL_label="labeled", FDL_type="covariance", useEnsemblePseudo=True, ema_decay=0.999, lr=2.5e-4,
         outRes=data.outRes, pck_ref=data.pck_ref, pck_thr=data.pck_thr, feature_mode="AvgPool", epo=0)
+    gated = a.pseudo_rule != "score"
+    if gated:                                                          # (a default run sets none of these)
+        args.pseudoRule, args.distThrMax = a.pseudo_rule, a.dist_thr
+        if a.pseudo_refine is not None:
+            args.pseudoRefine = a.pseudo_refine
+        if a.pseudo_blur_sigma is not None:
+            args.pseudoBlurSigma = a.pseudo_blur_sigma
     models, emas, optims = [], [], []
     for _ in range(2):                                                 # :43-50 student, teacher per branch
         models.append(pose_model(a.model, data.kpsCount, "AvgPool"))
@@ -87,16 +103,22 @@ def run(a, write=True, keep=None):
     def loader():
         for idx in sampler:
             idx = list(idx)
-            views, kps = [], []
+            views, kps, mats = [], [], []
             for _ in range(2):                                         # DS_mds augCount = 2
-                x, k = aug.views(idx, kps_all[idx])
+                x, k, *m = aug.views(idx, kps_all[idx], with_mats=gated)
                 views.append(x)
                 kps.append(k)
-            yield views, None, {"kps": kps, "islabeled": [torch.tensor(isl_all[idx], device=dev)]}
+                mats += m
+            meta = {"kps": kps, "islabeled": [torch.tensor(isl_all[idx], device=dev)]}
+            if gated:
+                meta["viewmat"] = mats
+            yield views, None, meta
 
     log = {"config": {"model": a.model, "trainBS": a.trainBS, "trainBS_labeled": a.trainBS_labeled,
                       "epochs": a.epochs, "augment": not a.no_aug, "seed": a.seed, "split": "Mouse_100_500_0.3",
-                      "pck_ref": data.pck_ref, "pck_thr": data.pck_thr, "means": means},
+                      "pck_ref": data.pck_ref, "pck_thr": data.pck_thr, "means": means,
+                      "pseudo_rule": a.pseudo_rule, "dist_thr": a.dist_thr, "pseudo_refine": a.pseudo_refine,
+                      "pseudo_blur_sigma": a.pseudo_blur_sigma},
            "epochs": []}
     best = (-1.0, -1)
     t0 = time.time()
@@ -106,10 +128,12 @@ def run(a, write=True, keep=None):
         args.FDLWeight = PR.FDLWeight_decrease(epo, args)
         args.pseudoWeight = PR.pseudoWeight_increase(epo, args)
         te = time.time()
-        pec, mtc, epc, fdc = T.train_mt_ubpl(loader(), models, emas, optims, args, verbose=False)
+        picked = {}                                                    # the steps' pseudo-label counts
+        pec, mtc, epc, fdc = T.train_mt_ubpl(loader(), models, emas, optims, args, verbose=False,
+                                             pseudo_counts=picked)
         torch.cuda.synchronize()
         rec = {"epoch": epo + 1, "train_s": round(time.time() - te, 2), "pec": pec, "mtc": mtc, "epc": epc,
-               "fdc": fdc}
+               "fdc": fdc, "sel_rate": round(picked["n_sel"] / picked["n_pseudo"], 4) if picked.get("n_pseudo") else None}
         if (epo + 1) % a.valid_every == 0 or epo + 1 == a.epochs:
             _, accs, errs = T.validate(vb, emas, args)
             rec["pck"] = [round(v[-1], 4) for v in accs]               # teacher 1, teacher 2, mean
@@ -121,6 +145,8 @@ def run(a, write=True, keep=None):
                 epo + 1, rec["pck"][0], rec["pck"][1], rec["pck"][2], time.time() - t0), flush=True)
         log["epochs"].append(rec)
     log["best_pck"], log["best_epoch"] = best
+    tail = [e["sel_rate"] for e in log["epochs"][-10:] if e["sel_rate"] is not None]
+    log["sel_rate_last10"] = round(sum(tail) / len(tail), 4) if tail else None
     log["final_pck"] = log["epochs"][-1]["pck"]
     log["wall_s"] = round(time.time() - t0, 1)
     if keep is not None:

@@ -82,6 +82,8 @@ __global__ void __launch_bounds__(256) row_grad_kernel(RowGeom g, int S, int K, 
 // kind 0: MSE / consistency   w = gate? * sw?                     (utils/losses.py:16-53)
 // kind 1: teacher-confidence  w = gate? * sw? * [tmax >= thr]     (utils/losses.py:255-286)
 // kind 2: UBPL pseudo mask    w = sw * [amax >= thr] * [tmax >= thr]  (utils/losses.py:176-210)
+// kind 3: kind 2 with a given selection: w = sw * [gate > 0] * [amax >= thr] * [tmax >= thr]; the
+//         gate [B,K] is a row mask only (cnt[0] stays kind 2's S*B*K)
 // cnt[0] = S * #{gate > 0}, cnt[1] = n_pseudo = #{pre-mask loss > 0},
 // cnt[2] = n_sel = #{mask > 0}, cnt[3] = #{rows with sw > 0}.
 __global__ void __launch_bounds__(256) finalize_kernel(int kind, const float* __restrict__ sq_mean,
@@ -105,6 +107,9 @@ __global__ void __launch_bounds__(256) finalize_kernel(int kind, const float* __
         if (kind == 2) {
             if (sw) l = l * sv;
             m = (amax[r] >= thr ? 1.f : 0.f) * (tmax[r] >= thr ? 1.f : 0.f);
+        } else if (kind == 3) {
+            if (sw) l = l * sv;
+            m = (gv > 0.f ? 1.f : 0.f) * (amax[r] >= thr ? 1.f : 0.f) * (tmax[r] >= thr ? 1.f : 0.f);
         } else {
             if (use_gate) l = l * gv;
             if (use_sw && sw) l = l * sv;
@@ -114,7 +119,7 @@ __global__ void __launch_bounds__(256) finalize_kernel(int kind, const float* __
         n_sel += m > 0.f;
         lsum += (double)(l * m);
         float wv = m;
-        if (kind == 2) {
+        if (kind == 2 || kind == 3) {
             if (sw) wv *= sv;
         } else {
             if (use_gate) wv *= gv;
@@ -122,7 +127,7 @@ __global__ void __launch_bounds__(256) finalize_kernel(int kind, const float* __
         }
         out_w[r] = wv;
     }
-    for (int r = threadIdx.x; r < B * K; r += blockDim.x) n_gate += (gate ? gate[r] : 1.f) > 0.f;
+    for (int r = threadIdx.x; r < B * K; r += blockDim.x) n_gate += (gate && kind != 3 ? gate[r] : 1.f) > 0.f;
     lsum = ubpl::block_sum(lsum, dred);
     n_pos = ubpl::block_sum(n_pos, ired);
     n_sel = ubpl::block_sum(n_sel, ired);
@@ -145,13 +150,13 @@ __global__ void __launch_bounds__(256) finalize_kernel(int kind, const float* __
                 for (int b = 0; b < B; ++b) {
                     if ((sw ? sw[b] : 1.f) > 0.f) {
                         const int r = (b * S + s) * K + k;
-                        if (kind == 2) sa += amax[r];
+                        if (kind >= 2) sa += amax[r];
                         st += tmax[r];
                     }
                 }
                 const float ma = n_rows > 0 ? sa / (float)n_rows : 0.f;
                 const float mt = n_rows > 0 ? st / (float)n_rows : 0.f;
-                acc_s += kind == 2 ? (ma + mt) / 2.f : mt;
+                acc_s += kind >= 2 ? (ma + mt) / 2.f : mt;
             }
             out_score[k] = acc_s / (float)S;
         }
@@ -263,6 +268,7 @@ UBPL_API int ubpl_loss_finalize(int kind, const float* sq_mean, const float* ama
                                 const float* gate, const float* sw, int use_gate, int use_sw, int B, int S, int K,
                                 float thr, float* out_sum, int* out_cnt, float* out_score, float* out_w,
                                 void* stream) {
+    if (kind < 0 || kind > 3 || (kind == 3 && gate == nullptr)) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, kind, sq_mean, amax, tmax, gate,
                        sw, use_gate, use_sw, B, S, K, thr, out_sum, out_cnt, out_score, out_w);
     UBPL_LAUNCH_CHECK();

@@ -22,6 +22,13 @@
 // m.  The data is a few hundred bytes per block: what matters is one launch inside the captured
 // graph and summation orders that a restatement can reproduce.  No atomics; contraction is off,
 // so every product and sum is its own f32 rounding; repeated launches give equal bits.
+//
+// The kernel is a template on how the points are addressed.  SAMPLES = false is the layout above:
+// one back[V,6] for all samples, view-major member blocks, the joint swap and tinv.  SAMPLES = true
+// (ubpl_view_uncertainty_samples) is the training step's: every (view, sample) has its own random
+// flip, scale and rotation, so back is [V][N][6]; raw has a member and a view stride (one decode
+// launch per view fills a [V][M][N][K][2] buffer); no joint swap and no tinv (points come out in
+// source-image pixels through back); and gate[N,K] = 1 iff every member is selected.
 #include "common.h"
 
 namespace {
@@ -37,18 +44,21 @@ __device__ __forceinline__ float dist2(float ax, float ay, float bx, float by) {
     return sqrtf(dx * dx + dy * dy);
 }
 
+template <bool SAMPLES>
 __global__ void __launch_bounds__(64) view_uncertainty_kernel(
-    const float* __restrict__ raw, int64_t sm, int M, int V, int N, int K, const float* __restrict__ back,
-    const int* __restrict__ swap, const int* __restrict__ perm, const double* __restrict__ tinv,
-    const float* __restrict__ dist_thr, float* __restrict__ pts, float* __restrict__ legal,
-    float* __restrict__ int_dist, float* __restrict__ aug_coord, float* __restrict__ ext_dist,
-    float* __restrict__ aext_dist, float* __restrict__ ext_views, float* __restrict__ mix_dist,
-    float* __restrict__ unc, float* __restrict__ select) {
+    const float* __restrict__ raw, int64_t sm, int64_t sv, int M, int V, int N, int K,
+    const float* __restrict__ back, const int* __restrict__ swap, const int* __restrict__ perm,
+    const double* __restrict__ tinv, const float* __restrict__ dist_thr, float* __restrict__ pts,
+    float* __restrict__ legal, float* __restrict__ int_dist, float* __restrict__ aug_coord,
+    float* __restrict__ ext_dist, float* __restrict__ aext_dist, float* __restrict__ ext_views,
+    float* __restrict__ mix_dist, float* __restrict__ unc, float* __restrict__ select,
+    float* __restrict__ gate) {
     __shared__ float s_x[MAX_MEMBERS * MAX_VIEWS], s_y[MAX_MEMBERS * MAX_VIEWS];
     __shared__ int s_ok[MAX_MEMBERS * MAX_VIEWS];
     __shared__ float s_int[MAX_MEMBERS], s_ax[MAX_MEMBERS], s_ay[MAX_MEMBERS];
     __shared__ int s_leg[MAX_MEMBERS];
     __shared__ float s_pair[3];
+    __shared__ int s_sel[MAX_MEMBERS];
     const int map = blockIdx.x, lane = threadIdx.x;
     const int n = map / K, k = map - n * K;
     const int64_t maps = (int64_t)N * K;
@@ -56,19 +66,25 @@ __global__ void __launch_bounds__(64) view_uncertainty_kernel(
     // the points, in the original frame (heatmap cells, or image coordinates with tinv)
     for (int i = lane; i < M * V; i += 64) {
         const int m = i / V, v = i - m * V;
-        int kk = k;
-        if (swap != nullptr && swap[v] != 0 && perm != nullptr) {
-            const int pk = perm[k];
-            if ((unsigned)pk < (unsigned)K) kk = pk;      // (a bad table must not read out of bounds)
+        const float *p, *b;
+        if (SAMPLES) {
+            p = raw + m * sm + v * sv + ((int64_t)n * K + k) * 2;
+            b = back + ((int64_t)v * N + n) * 6;
+        } else {
+            int kk = k;
+            if (swap != nullptr && swap[v] != 0 && perm != nullptr) {
+                const int pk = perm[k];
+                if ((unsigned)pk < (unsigned)K) kk = pk;  // (a bad table must not read out of bounds)
+            }
+            p = raw + m * sm + (((int64_t)v * N + n) * K + kk) * 2;
+            b = back + v * 6;
         }
-        const float* p = raw + m * sm + (((int64_t)v * N + n) * K + kk) * 2;
         const float rx = p[0], ry = p[1];
         const float u = rx - 1.f, w = ry - 1.f;
-        const float* b = back + v * 6;
         const float ox = (b[0] * u + b[1] * w) + b[2];
         const float oy = (b[3] * u + b[4] * w) + b[5];
         float px, py;
-        if (tinv != nullptr) {
+        if (!SAMPLES && tinv != nullptr) {
             // ubpl_refine_peaks' preds_sub expression at (ox, oy): f64, un-fused, + 1, not truncated
             const double* t = tinv + (int64_t)n * 6;
             const double du = (double)ox, dw = (double)oy;
@@ -82,7 +98,7 @@ __global__ void __launch_bounds__(64) view_uncertainty_kernel(
         }
         const bool peak = !(rx == 0.f && ry == 0.f);
         const bool finite = fabsf(px) < INFINITY && fabsf(py) < INFINITY;      // false on a NaN
-        const bool ok = peak && finite && (tinv == nullptr || (px >= 0.f && py >= 0.f));   // business.py:31
+        const bool ok = peak && finite && (SAMPLES || tinv == nullptr || (px >= 0.f && py >= 0.f));   // business.py:31
         s_x[i] = px;
         s_y[i] = py;
         s_ok[i] = ok ? 1 : 0;
@@ -149,25 +165,34 @@ __global__ void __launch_bounds__(64) view_uncertainty_kernel(
     }
     __syncthreads();
 
-    if (lane >= M) return;                                             // (past the last barrier)
-    const float e = s_pair[0], ae = s_pair[1], t = dist_thr[0];
-    float mix = SENTINEL, un = SENTINEL;
-    bool sel = false;
-    if (leg) {
-        mix = id + (e > 0.f ? (e + ae) / 2.f : ae);                    // :328
-        un = 1.f - expf(-mix / 5.f);                                   // _calUncValue (:375-376)
-        sel = id <= t && e <= t && ae <= t && mix <= 3.f * t;          // :331-345, :242-247 on the distance
+    if (lane < M) {
+        const float e = s_pair[0], ae = s_pair[1], t = dist_thr[0];
+        float mix = SENTINEL, un = SENTINEL;
+        bool sel = false;
+        if (leg) {
+            mix = id + (e > 0.f ? (e + ae) / 2.f : ae);                // :328
+            un = 1.f - expf(-mix / 5.f);                               // _calUncValue (:375-376)
+            sel = id <= t && e <= t && ae <= t && mix <= 3.f * t;      // :331-345, :242-247 on the distance
+        }
+        const int64_t o = (int64_t)lane * maps + map;
+        if (legal != nullptr) legal[o] = leg ? 1.f : 0.f;
+        if (int_dist != nullptr) int_dist[o] = id;
+        if (aug_coord != nullptr) {
+            aug_coord[o * 2] = ax;
+            aug_coord[o * 2 + 1] = ay;
+        }
+        if (mix_dist != nullptr) mix_dist[o] = mix;
+        if (unc != nullptr) unc[o] = un;
+        select[o] = sel ? 1.f : 0.f;
+        if (SAMPLES) s_sel[lane] = sel ? 1 : 0;
     }
-    const int64_t o = (int64_t)lane * maps + map;
-    if (legal != nullptr) legal[o] = leg ? 1.f : 0.f;
-    if (int_dist != nullptr) int_dist[o] = id;
-    if (aug_coord != nullptr) {
-        aug_coord[o * 2] = ax;
-        aug_coord[o * 2 + 1] = ay;
+    if (!SAMPLES || gate == nullptr) return;                           // (uniform over the block)
+    __syncthreads();
+    if (lane == 0) {
+        bool all = true;                                               // unc_select.all(0)
+        for (int m = 0; m < M; ++m) all = all && s_sel[m] != 0;
+        gate[map] = all ? 1.f : 0.f;
     }
-    if (mix_dist != nullptr) mix_dist[o] = mix;
-    if (unc != nullptr) unc[o] = un;
-    select[o] = sel ? 1.f : 0.f;
 }
 
 }  // namespace
@@ -185,9 +210,36 @@ UBPL_API int ubpl_view_uncertainty(const float* raw, int64_t sm, int M, int V, i
         return (int)hipErrorInvalidValue;
     const int maps = N * K;
     if (maps == 0) return 0;
-    hipLaunchKernelGGL(view_uncertainty_kernel, dim3(maps), dim3(64), 0, (hipStream_t)stream, raw, sm, M, V, N, K,
-                       back, swap, perm, tinv, dist_thr, pts, legal, int_dist, aug_coord, ext_dist, aext_dist,
-                       ext_views, mix_dist, unc, select);
+    hipLaunchKernelGGL(view_uncertainty_kernel<false>, dim3(maps), dim3(64), 0, (hipStream_t)stream, raw, sm,
+                       (int64_t)0, M, V, N, K, back, swap, perm, tinv, dist_thr, pts, legal, int_dist, aug_coord,
+                       ext_dist, aext_dist, ext_views, mix_dist, unc, select, (float*)nullptr);
+    UBPL_LAUNCH_CHECK();
+    return 0;
+}
+
+// The same rule with per-sample matrices (see include/ubpl_hip.h): member m's point of view v,
+// sample n, joint k at raw + m*sm + v*sv + (n*K + k)*2, its matrix at back + (v*N + n)*6.
+UBPL_API int ubpl_view_uncertainty_samples(const float* raw, int64_t sm, int64_t sv, int M, int V, int N, int K,
+                                           const float* back, const float* dist_thr, float* pts, float* legal,
+                                           float* int_dist, float* aug_coord, float* ext_dist, float* aext_dist,
+                                           float* ext_views, float* mix_dist, float* unc, float* select,
+                                           float* gate, void* stream) {
+    if (M < 1 || M > MAX_MEMBERS || V < 2 || V > MAX_VIEWS || N < 0 || K < 1 || (int64_t)N * K > 0x3fffffff ||
+        (int64_t)V * N * K > 0x3fffffff || raw == nullptr || back == nullptr || dist_thr == nullptr ||
+        select == nullptr)
+        return (int)hipErrorInvalidValue;
+    // a view's block of one member holds N*K points; the members' and the views' blocks do not
+    // interleave: member-major (sm >= the V views of a member) or view-major (sv >= the M members)
+    // (strides are bounded first, so that the products below cannot wrap)
+    const int64_t blk = (int64_t)N * K * 2, max_stride = (int64_t)1 << 40;
+    if (sm > max_stride || sv > max_stride || sv < blk || sm < 0 || (M > 1 && sm < blk) ||
+        (M > 1 && sm < (V - 1) * sv + blk && sv < (M - 1) * sm + blk))
+        return (int)hipErrorInvalidValue;
+    const int maps = N * K;
+    if (maps == 0) return 0;
+    hipLaunchKernelGGL(view_uncertainty_kernel<true>, dim3(maps), dim3(64), 0, (hipStream_t)stream, raw, sm, sv, M,
+                       V, N, K, back, (const int*)nullptr, (const int*)nullptr, (const double*)nullptr, dist_thr,
+                       pts, legal, int_dist, aug_coord, ext_dist, aext_dist, ext_views, mix_dist, unc, select, gate);
     UBPL_LAUNCH_CHECK();
     return 0;
 }

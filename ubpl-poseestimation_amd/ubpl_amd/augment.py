@@ -320,11 +320,14 @@ class DeviceAugment:
         return draw_view(kps, self.W, self.H, self.res, self.sf, self.rf, self.use_flip, self.use_noise,
                          with_geometry=True)
 
-    def views(self, idx, kps, occlusion=None, occ_rate=0.5, num_occluder=8):
+    def views(self, idx, kps, occlusion=None, occ_rate=0.5, num_occluder=8, with_mats=False):
         """idx: source image per view [V]; kps: numpy [V,K,3] pixel keypoints;
         occlusion: an OcclusionBank (DS_mds useOcclusion, datasets/dataset_mds.py:
         104-109: drawn after each view's affine, as the loader does).
-        -> (images [V,3,res,res] on the device, keypoints [V,K,3] on the device)."""
+        -> (images [V,3,res,res] on the device, keypoints [V,K,3] on the device); with_mats: and
+        the [V,6] float32 device matrices of the views (warp_matrix: 0-based view pixel -> 0-based
+        source-image pixel), which the view-consistency rule of the training step maps peaks back
+        with (meta["viewmat"]).  The random draws and their order are the same either way."""
         mats, noises, out_k, geos, css = [], [], [], [], []
         pastes, first = [], [0]
         for v, k in enumerate(kps):
@@ -357,4 +360,5 @@ class DeviceAugment:
             pt = np.array([p[:8] + (p[8] | (p[9] << 16),) for p in pastes], np.int32)
             Kn.occlude(out, occlusion.bank, occlusion.off, occlusion.hw, torch.from_numpy(pt).to(self.dev),
                        torch.tensor(first, dtype=torch.int32, device=self.dev), self.chan_mean)
-        return out, torch.tensor(np.array(out_k, np.float32), device=self.dev)
+        out_k = torch.tensor(np.array(out_k, np.float32), device=self.dev)
+        return (out, out_k, mat) if with_mats else (out, out_k)

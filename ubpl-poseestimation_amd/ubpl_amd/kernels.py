@@ -98,6 +98,10 @@ def row_stats(g, want_amax=False, want_tmax=False):
 
 def loss_finalize(kind, sq, amax, tmax, gate, sw, use_gate, use_sw, B, S, K, thr):
     dev = sq.device
+    if kind == 3:                                               # the pseudo mask with a given selection
+        _chk(gate, "gate")
+        if gate is None or gate.numel() != B * K:
+            raise ValueError("ubpl_amd: loss_finalize kind 3 takes a gate of [B,K] = %d x %d entries" % (B, K))
     out_sum = torch.empty(1, device=dev, dtype=F32)
     out_cnt = torch.empty(4, device=dev, dtype=torch.int32)
     score = torch.empty(K, device=dev, dtype=F32) if kind != 0 else None
@@ -491,6 +495,71 @@ def view_uncertainty(raw, sm, M, V, N, K, back, dist_thr, swap=None, perm=None, 
         raise ValueError("ubpl_amd: view_uncertainty always writes select")
     call("ubpl_view_uncertainty", raw, int(sm), M, V, N, K, back, swap, perm, tinv, dist_thr, *outs)
     return outs
+
+
+def view_uncertainty_samples(raw, sm, sv, M, V, N, K, back, dist_thr, out=None):
+    """view_uncertainty where every (view, sample) has its own matrix (ubpl_view_uncertainty_samples;
+    the training step's augmented views): member m's point of view v, sample n, joint k is the pair
+    at raw[m*sm + v*sv + (n*K + k)*2] — a [V,M,N,K,2] buffer has sm = N*K*2, sv = M*N*K*2 — and
+    back: device float32 [V,N,6] (train_back_matrices).  No swap / perm / tinv: the points come out
+    in the frame back maps to.  dist_thr: device float32 [1].  1 <= M <= 8, 2 <= V <= 16.
+    -> view_uncertainty's ten outputs and gate [N,K] = 1 where every member is selected;
+    out = the same eleven: write into these instead of allocating (None: not wanted; select is
+    required)."""
+    if not 1 <= M <= 8:
+        raise ValueError("ubpl_amd: view_uncertainty_samples takes 1 to 8 members, got %d" % M)
+    if not 2 <= V <= MAX_VIEWS:
+        raise ValueError("ubpl_amd: view_uncertainty_samples takes 2 to %d views, got %d" % (MAX_VIEWS, V))
+    _chk(raw, "raw")
+    blk = N * K * 2
+    need = (M - 1) * sm + (V - 1) * sv + blk
+    nested = M == 1 or sm >= (V - 1) * sv + blk or sv >= (M - 1) * sm + blk
+    if raw is None or sm < 0 or sv < blk or (M > 1 and sm < blk) or not nested or raw.numel() < need:
+        raise ValueError("ubpl_amd: raw holds %d floats, %d members of stride %d and %d views of stride %d with "
+                         "%d x %d points need %d" % (0 if raw is None else raw.numel(), M, sm, V, sv, N, K, need))
+    _chk(back, "back")
+    _chk(dist_thr, "dist_thr")
+    if back is None or back.numel() != V * N * 6:
+        raise ValueError("ubpl_amd: back is [V,N,6], one pixel matrix per view and sample")
+    if dist_thr is None or dist_thr.numel() != 1:
+        raise ValueError("ubpl_amd: dist_thr is a device float32 tensor of one element")
+    _chk_entries(None, K, None)
+    mnk, nk = (M, N, K), (N, K)                                 # (UNC_OUTPUTS' order, then gate)
+    outs = _outs(out, raw.device, *((shape, True) for shape in ((M, V, N, K, 2), mnk, mnk, (M, N, K, 2), nk, nk, nk,
+                                                                mnk, mnk, mnk, nk)))
+    if len(outs) != len(UNC_OUTPUTS) + 1:
+        raise ValueError("ubpl_amd: view_uncertainty_samples writes %d outputs, got %d"
+                         % (len(UNC_OUTPUTS) + 1, len(outs)))
+    if outs[-2] is None:
+        raise ValueError("ubpl_amd: view_uncertainty_samples always writes select")
+    call("ubpl_view_uncertainty_samples", raw, int(sm), int(sv), M, V, N, K, back, dist_thr, *outs)
+    return outs
+
+
+def train_back_matrices(viewmat, R, H):
+    """The back matrices of the training step's views for view_uncertainty_samples.
+    viewmat: [V,N,6] (or a list of V [N,6]) float32, DeviceAugment.views(with_mats=True)'s matrices
+    (warp_matrix: 0-based view input pixel -> 0-based source-image pixel), on any device; R the
+    views' input side, H the heatmaps'.  -> float32 [V,N,6] on viewmat's device: 0-based heatmap
+    cell -> source-image pixel, back = viewmat o C.
+
+    The cell convention C is the renderer's, inverted.  render_batch centres the Gaussian of a
+    keypoint at view pixel x on the 0-based cell x / (R/H) (csrc/render.hip: cx = trunc(x) /
+    stride), so C(c) = (R/H) c on both axes, and a decoded 1-based peak raw enters the kernel as
+    c = raw - 1.  The keypoint coordinates the loader hands the renderer are taken as the view's
+    pixel coordinates, as the renderer takes them; the reference's keypoint path (transform_point:
+    p - 1, the float64 product truncated, + 1; kps_fliplr: W - x) lands within a pixel of where
+    warp_matrix puts the same source pixel (DESIGN.md §4 has the measured offsets).
+    Composed in float64 and rounded once to float32, as compose_pixels does, with tensor ops only:
+    on the device it needs no host synchronisation and can be captured."""
+    m = torch.stack(list(viewmat)) if isinstance(viewmat, (list, tuple)) else viewmat
+    if m.dim() != 3 or m.shape[-1] != 6:
+        raise ValueError("ubpl_amd: viewmat is [V,N,6], one pixel matrix per view and sample")
+    m = m.to(F64)
+    s = float(R) / float(H)
+    out = m * s                                                 # the linear part: a cell is R/H pixels
+    out[..., 2::3] = m[..., 2::3]                               # C has no offset: the translation stays
+    return out.to(F32).contiguous()
 
 
 def fliplr(x, out=None):

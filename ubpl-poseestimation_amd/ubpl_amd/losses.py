@@ -43,7 +43,7 @@ class _RowLoss(torch.autograd.Function):
     def forward(ctx, a, t, spec, gate, sw):
         kind, S, K, HW, tg, use_gate, use_sw, thr = spec
         g = _geom(a, S, K, HW, t, *tg)
-        sq, am, tm = Kn.row_stats(g, want_amax=(kind == 2), want_tmax=(kind != 0))
+        sq, am, tm = Kn.row_stats(g, want_amax=(kind in (2, 3)), want_tmax=(kind != 0))
         s, cnt, score, w = Kn.loss_finalize(kind, sq, am, tm, gate, sw, use_gate, use_sw, a.shape[0], S, K, thr)
         ctx.save_for_backward(a, t, w)
         ctx.spec = spec

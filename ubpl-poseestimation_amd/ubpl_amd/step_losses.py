@@ -64,6 +64,19 @@ def _pseudo(preds, targets, sw, S, thr):
     return _RowLoss.apply(preds, targets, spec, None, sw)
 
 
+def _pseudo_gated(preds, targets, sw, S, thr, gate):
+    """_pseudo with a given selection (ubpl_loss_finalize kind 3): gate [B,K] device float32, > 0 =
+    the joint's pseudo label is kept; the row mask is gate * the two score tests at thr
+    (thr = -inf: the gate alone; a NaN score still never selects)."""
+    B, K = preds.shape[0], preds.shape[2]
+    HW = preds.shape[-1] * preds.shape[-2]
+    M, St = targets.shape[0], targets.shape[2]
+    if gate is None or gate.numel() != B * K:
+        raise ValueError("ubpl_amd: _pseudo_gated takes a gate of [B,K] = %d x %d entries" % (B, K))
+    spec = (3, S, K, HW, (St * K * HW, 0, B * St * K * HW, M, (St - 1) * K * HW), False, True, float(thr))
+    return _RowLoss.apply(preds, targets, spec, gate, sw)
+
+
 def _norm(s, n):
     """(s / n) if n > 0 else s — with n a device tensor."""
     n = n.float()

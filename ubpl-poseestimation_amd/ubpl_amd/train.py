@@ -31,14 +31,15 @@ import os
 import torch
 
 from . import dist as D
+from . import view_gate as VG
 from .guard import _configure_guard, _gd, _guard_and_restore, _guard_nets, _save_stats, _SkipWatch
 from .losses import AvgCounter
 from .parameters import ema_alpha, update_ema_variables
 from .process import render_batch
 from .step_graph import _collective, _drive, _LaggedRecords, _StepGraph  # noqa: F401
 from .step_losses import (_dist_last, _dist_mt2_last, _fdl_record, _fdl_record_sums, _fdl_rows,  # noqa: F401
-                          _fdl_total, _fdl_view, _islabeled, _mse, _mse_plain, _norm, _pseudo, _RecordLayout,
-                          _targets, _w)
+                          _fdl_total, _fdl_view, _islabeled, _mse, _mse_plain, _norm, _pseudo, _pseudo_gated,
+                          _RecordLayout, _targets, _w)
 from .streams import _backward_all, _join_merge, _ModelStreams, _OnMain, _PhaseCheck  # noqa: F401
 from .validation import fold_valid_rows, gather_valid_rows, valid_batch_row, validate  # noqa: F401
 
@@ -140,9 +141,11 @@ def _pseudo_rate(n_sel, n_ps, guarded=False):
     return int(n_sel) / int(n_ps)
 
 
-def _pseudo_line(bat, kind, args, rate, n_sel, n_ps, scores):
+def _pseudo_line(bat, kind, args, rate, n_sel, n_ps, scores, dist_thr=None):
+    """dist_thr: the view-consistency rule's threshold, shown only when that rule is on."""
+    thr = format(args.pseudoScoreThr, ".2f") + ("" if dist_thr is None else " distThr:" + format(dist_thr, ".2f"))
     print("batch.{}{} (scoreThr:{}): {} ({}/{}), pseudo-score: [{}]".format(
-        format(bat + 1, "5d"), kind, format(args.pseudoScoreThr, ".2f"), format(rate, ".2f"),
+        format(bat + 1, "5d"), kind, thr, format(rate, ".2f"),
         format(n_sel, "5d"), format(n_ps, "5d"), ", ".join(format(v, ".3f") for v in scores)))
 
 
@@ -160,10 +163,15 @@ def _mt_ubpl_core(models, models_ema, optims, args, augs_imgMap, augs_heatmaps, 
     M = len(models)
     dev = models[0].flat_params.device
     S = args.nStack
+    A = len(augs_imgMap)
+    use_ep = getattr(args, "useEnsemblePseudo", True)        # :271 (False: epc = 0, no print)
+    rule = VG.options(args)                              # the view-consistency rule (off: the score rule)
+    gated = rule.on and use_ep
+    if gated:
+        VG.check_batch(rule, meta, A, M)                     # ValueError before any launch
     for o in optims:
         o.zero_grad()
     _save_stats(optims, _guard_nets(models, models_ema))
-    A = len(augs_imgMap)
     imgs = [x.to(dev, non_blocking=True).float().contiguous() for x in augs_imgMap]
     hms, gates = _targets(imgs, augs_heatmaps, meta, A, dev, args)
     isl = _islabeled(meta["islabeled"][0], dev)
@@ -198,9 +206,14 @@ def _mt_ubpl_core(models, models_ema, optims, args, augs_imgMap, augs_heatmaps, 
         outs = [[_OnMain.apply(t) for t in ts] for ts in outs]
         feats = [[None if t is None else _OnMain.apply(t) for t in ts] for ts in feats]
     K = outs[0][0].shape[2]
-    use_ep = getattr(args, "useEnsemblePseudo", True)        # :271 (False: epc = 0, no print)
     zero = torch.zeros((), device=dev)
     zcnt = torch.zeros(4, dtype=torch.int32, device=dev)
+    if gated:
+        # the teachers' stacked outputs per view, built once: decoded for the gate here, on the
+        # main stream after the join, and shared by the students' pseudo losses below
+        with torch.no_grad():
+            tgs = [torch.stack([outs_ema[j][a] for j in range(M)]) for a in range(A)]
+            gate = VG.view_gate(rule, tgs, meta["viewmat"], imgs[0].shape[-1])
     # ---- loss sums / counts on device
     sums, ps_scores = [], []
     for mi in range(M):
@@ -208,7 +221,10 @@ def _mt_ubpl_core(models, models_ema, optims, args, augs_imgMap, augs_heatmaps, 
         for a in range(A):
             s_d, _ = _dist_last(outs[mi][a], outs_ema[mi][a])
             s_p, c_p = _mse(outs[mi][a], hms[a], S, gates[a], sw.reshape(-1, 1))
-            if use_ep:
+            if gated:
+                s_e, c_e, sc_e = _pseudo_gated(outs[mi][a], tgs[a], nega, S, rule.thr, gate)
+                ps_scores.append(sc_e)
+            elif use_ep:
                 tg = torch.stack([outs_ema[j][a] for j in range(M)])
                 s_e, c_e, sc_e = _pseudo(outs[mi][a], tg, nega, S, args.pseudoScoreThr)
                 ps_scores.append(sc_e)
@@ -275,14 +291,28 @@ def _mt_ubpl_records(host, bat, L, mtc_n, B, use_ep, counters, args, verbose, gu
         # raises ZeroDivisionError there, and here when its records are consumed
         rate = _pseudo_rate(n_sel, n_ps, guarded)
         if verbose:
-            _pseudo_line(bat, "", args, rate, n_sel, n_ps, host[L.scores()])
+            rule = VG.options(args)
+            _pseudo_line(bat, "", args, rate, n_sel, n_ps, host[L.scores()], rule.dist_thr if rule.on else None)
 
 
-def train_mt_ubpl(trainLoader, models, models_ema, optims, args, verbose=True):
+def train_mt_ubpl(trainLoader, models, models_ema, optims, args, verbose=True, pseudo_counts=None):
     """projects/MT_UBPL.py:157-352 -> (pec_records, mtc_records, epc_records, fdc_record).
     Steps after the first two are replayed from a captured HIP graph when the
-    batch shapes repeat (UBPL_STEP_GRAPH=0: every step eager)."""
-    return _train_steps(_mt_ubpl_core, _mt_ubpl_records, trainLoader, models, models_ema, optims, args, verbose)
+    batch shapes repeat (UBPL_STEP_GRAPH=0: every step eager).
+    args.pseudoRule "uncertainty" / "score+uncertainty" (with args.distThrMax; pseudoRefine,
+    pseudoBlurSigma) selects the pseudo labels by the view-consistency rule (view_gate.py); the
+    batches then carry meta["viewmat"].  pseudo_counts: a dict that receives the epoch's totals of
+    the steps' pseudo-label counts, "n_pseudo" and "n_sel" (what the active rule selected)."""
+    rule = VG.options(args)
+    if rule.on:
+        VG.constants(rule, models[0].flat_params.device)     # host -> device, ahead of any capture
+
+    def records(host, bat, L, mtc_n, B, use_ep, *rest):
+        if pseudo_counts is not None and use_ep:             # the step's own counts, summed over the epoch
+            pseudo_counts["n_sel"] = pseudo_counts.get("n_sel", 0) + L.total(host, "n_sel")
+            pseudo_counts["n_pseudo"] = pseudo_counts.get("n_pseudo", 0) + L.total(host, "epc_n")
+        return _mt_ubpl_records(host, bat, L, mtc_n, B, use_ep, *rest)
+    return _train_steps(_mt_ubpl_core, records, trainLoader, models, models_ema, optims, args, verbose)
 
 
 # ---------------------------------------------------------------------------
@@ -294,6 +324,7 @@ def _dualpose_core(models, models_ema, optims, args, stu_imgMap, stu_heatmap, em
     its two exchanges under torch.distributed and returns the packed records
     [3M+1 losses | counts | consistency scores | pseudo scores], their
     _RecordLayout and the host-side constants the layout cannot carry."""
+    VG.refuse(args, "train_dualpose_ubpl")
     M = len(models)
     dev = models[0].flat_params.device
     S = args.nStack
@@ -406,6 +437,7 @@ def train_dualpose_ubpl(trainLoader, models, models_ema, optims, args, verbose=T
 # ---------------------------------------------------------------------------
 def train_mt(trainLoader, model, model_ema, optim, args):
     """projects/MT.py:161-268 -> (pec_avg, mtc_avg)."""
+    VG.refuse(args, "train_mt")
     pec_c, mtc_c = AvgCounter(), AvgCounter()
     dev = model.flat_params.device
     S = args.nStack
