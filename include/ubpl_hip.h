@@ -75,6 +75,46 @@ int ubpl_heatmap_row_grad(const float* a, int64_t a_sb, int64_t a_ss, const floa
                           int64_t t_sm, int M, int B, int S, int K, int HW, const float* w, const float* gscale,
                           float extra, float* da, int accumulate, void* stream);
 
+/* ------------------------------------------------------------- L2b-L2d ---
+ * Softmax-score and rank-based pseudo-label selection: JointPseudoLoss, JointPseudoLoss2,
+ * JointDistLoss_mt (utils/losses.py:73-115, 118-166, 213-243).
+ *
+ * The reference's confidence score of a map (:137-138): softmax ACROSS the K maps of (b,s) at
+ * every pixel, then the per-map maximum.  Map (b,s,k) = mean over m < M of
+ * x + m*x_sm + b*x_sb + s*x_ss + k*HW, summed in member order and divided by (float)M (the
+ * target addressing of ubpl_heatmap_row_stats; M = 1: the maps themselves).
+ * score[B*S*K] = max_px exp(v_k - max_j v_j) / sum_j exp(v_j - max_j v_j).  One read of x.
+ * 1 <= K <= 32, 1 <= M <= 8 (hipErrorInvalidValue outside).  A NaN or +inf at a pixel makes
+ * the K scores of its (b,s) NaN. */
+/*@ x:f32[(M-1)*x_sm+(B-1)*x_sb+(S-1)*x_ss+(int64_t)K*HW] score:f32[B*S*K] */
+int ubpl_softmax_peak_scores(const float* x, int64_t x_sb, int64_t x_ss, int64_t x_sm, int M, int B, int S, int K,
+                             int HW, float* score, void* stream);
+/* thr[g] = the rank-th smallest (0-based) of scores[g*N .. g*N+N), bit for bit
+ * torch.sort(scores[g])[0][rank]: ties are values, NaNs order last.  One workgroup per group,
+ * by counting.  1 <= N <= 8192, 0 <= rank < N (hipErrorInvalidValue outside). */
+/*@ scores:f32[(int64_t)G*N] thr:f32[G] */
+int ubpl_rank_threshold(const float* scores, int G, int N, int rank, float* thr, void* stream);
+/* ubpl_loss_finalize for kinds 1 and 2 with the scores given and the thresholds read from
+ * device memory per stack: row mask (ascore >= athr[s]) * (tscore >= tthr[s]) for kind 2,
+ * tscore >= tthr[s] for kind 1 (ascore, athr nullable).  A NaN score or threshold never
+ * selects.  Outputs as ubpl_loss_finalize's (out_score from the given scores, nullable), so
+ * ubpl_heatmap_row_grad serves the backward with out_w. */
+/*@ sq_mean:f32[B*S*K] ascore:f32[B*S*K] tscore:f32[B*S*K] athr:f32[S] tthr:f32[S] gate:f32[B*K] sw:f32[B] out_sum:f32[1] out_cnt:i32[4] out_score:f32[K] out_w:f32[B*S*K] */
+int ubpl_loss_finalize_ranked(int kind, const float* sq_mean, const float* ascore, const float* tscore,
+                              const float* athr, const float* tthr, const float* gate, const float* sw,
+                              int use_gate, int use_sw, int B, int S, int K, float* out_sum, int* out_cnt,
+                              float* out_score, float* out_w, void* stream);
+/* The training step's form of the two above in one launch: per stack s the thresholds are the
+ * rank-th smallest of the batch's B*K scores ascore[b][s][k] (kind 2) and tscore[b][s][k];
+ * tscore holds t_stacks = S stacks, or 1 when one target map per (b,k) serves every stack.
+ * thr[2*S] receives them: athr[S] (NaN for kind 1), then tthr[S].  Everything else as
+ * ubpl_loss_finalize_ranked.  B*K <= 8192, 0 <= rank < B*K, S <= 16 (hipErrorInvalidValue outside). */
+/*@ sq_mean:f32[B*S*K] ascore:f32[B*S*K] tscore:f32[B*t_stacks*K] gate:f32[B*K] sw:f32[B] thr:f32[2*S] out_sum:f32[1] out_cnt:i32[4] out_score:f32[K] out_w:f32[B*S*K] */
+int ubpl_loss_finalize_rank(int kind, const float* sq_mean, const float* ascore, const float* tscore, int t_stacks,
+                            int rank, const float* gate, const float* sw, int use_gate, int use_sw, int B, int S,
+                            int K, float* thr, float* out_sum, int* out_cnt, float* out_score, float* out_w,
+                            void* stream);
+
 /* ---------------------------------------------------------------- L5 ----
  * ProcessUtils.features_cov (utils/process.py:18-31) over rows whose
  * rowmask[b] > 0 (the caller's labeled-row selection, projects/MT_UBPL.py:309-320).

@@ -10,8 +10,11 @@ the fused train step, HIP decode + PCK.
 
 --pseudo-rule uncertainty / score+uncertainty (with --dist-thr, source-image pixels) selects the
 pseudo labels by the view-consistency rule of the training step; the loader then
-hands the views' matrices on as meta["viewmat"].  Every run logs the share of pseudo labels its
-rule selected per epoch ("sel_rate").
+hands the views' matrices on as meta["viewmat"].  --pseudo-rule rate (with --sel-rate R, a share in
+(0, 1]) keeps the top share R of every batch's joints by softmax score (JointPseudoLoss2 in the
+step, DESIGN.md §4 "Rank-based pseudo-label selection") and logs each epoch's selection count
+("n_sel") and mean thresholds ("rate_thr1", "rate_thr2").  Every run logs the share of pseudo
+labels its rule selected per epoch ("sel_rate").
 
 Reads tests/golden/mouse_100_500_0.3/ (tools/pack_mouse.py).
 """
@@ -40,8 +43,9 @@ def parser():
     ap.add_argument("--valid-every", type=int, default=5)
     ap.add_argument("--no-aug", action="store_true")
     ap.add_argument("--seed", type=int, default=1388)
-    ap.add_argument("--pseudo-rule", default="score", choices=["score", "uncertainty", "score+uncertainty"])
+    ap.add_argument("--pseudo-rule", default="score", choices=["score", "uncertainty", "score+uncertainty", "rate"])
     ap.add_argument("--dist-thr", type=float, default=None, help="distThrMax, source-image pixels")
+    ap.add_argument("--sel-rate", type=float, default=None, help="pseudoSelRate of --pseudo-rule rate, in (0, 1]")
     ap.add_argument("--pseudo-refine", default=None, choices=["none", "quarter", "taylor"])
     ap.add_argument("--pseudo-blur-sigma", type=float, default=None)
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "mouse_pck.json"))
@@ -80,7 +84,9 @@ def run(a, write=True, keep=None):
         FDLWeight_rampup=100, pseudoWeight_max=1.0, pseudoWeight_min=1.0, pseudoWeight_rampup=100,
         FDL_label="labeled", FDL_type="covariance", useEnsemblePseudo=True, ema_decay=0.999, lr=2.5e-4,
         outRes=data.outRes, pck_ref=data.pck_ref, pck_thr=data.pck_thr, feature_mode="AvgPool", epo=0)
-    gated = a.pseudo_rule != "score"
+    gated = a.pseudo_rule not in ("score", "rate")
+    if a.pseudo_rule == "rate":
+        args.pseudoRule, args.pseudoSelRate = "rate", a.sel_rate
     if gated:                                                          # (a default run sets none of these)
         args.pseudoRule, args.distThrMax = a.pseudo_rule, a.dist_thr
         if a.pseudo_refine is not None:
@@ -118,7 +124,7 @@ def run(a, write=True, keep=None):
                       "epochs": a.epochs, "augment": not a.no_aug, "seed": a.seed, "split": "Mouse_100_500_0.3",
                       "pck_ref": data.pck_ref, "pck_thr": data.pck_thr, "means": means,
                       "pseudo_rule": a.pseudo_rule, "dist_thr": a.dist_thr, "pseudo_refine": a.pseudo_refine,
-                      "pseudo_blur_sigma": a.pseudo_blur_sigma},
+                      "pseudo_blur_sigma": a.pseudo_blur_sigma, "pseudo_sel_rate": a.sel_rate},
            "epochs": []}
     best = (-1.0, -1)
     t0 = time.time()
@@ -134,6 +140,10 @@ def run(a, write=True, keep=None):
         torch.cuda.synchronize()
         rec = {"epoch": epo + 1, "train_s": round(time.time() - te, 2), "pec": pec, "mtc": mtc, "epc": epc,
                "fdc": fdc, "sel_rate": round(picked["n_sel"] / picked["n_pseudo"], 4) if picked.get("n_pseudo") else None}
+        if picked.get("steps"):                                        # the "rate" rule: count and thresholds
+            rec["n_sel"] = picked["n_sel"]
+            rec["rate_thr1"] = round(picked["rate_thr1"] / picked["steps"], 6)
+            rec["rate_thr2"] = round(picked["rate_thr2"] / picked["steps"], 6)
         if (epo + 1) % a.valid_every == 0 or epo + 1 == a.epochs:
             _, accs, errs = T.validate(vb, emas, args)
             rec["pck"] = [round(v[-1], 4) for v in accs]               # teacher 1, teacher 2, mean

@@ -1,4 +1,5 @@
-"""What the view-consistency pseudo-label rule costs on the headline training step.
+"""What a pseudo-label rule of the training step costs on the headline step: the view-consistency
+rule (--rule uncertainty, the default) or the rank-based one (--rule rate).
 
 The bench's MT_UBPL step (2 students + 2 EMA teachers, HG2, 256x256, B=32, synthetic
 batches, captured in a HIP graph) with args.pseudoRule off ("score") and on
@@ -11,10 +12,14 @@ host clock around work that ends in a device synchronise; per variant the median
 rounds and the spread (max - min) / median across them.  The variants share the networks
 and optimizers; switching re-captures the step (untimed).  The synthetic batches carry a
 random similarity per (view, sample) as meta["viewmat"] (the rule's cost does not depend
-on what the matrices say).  One JSON line on stdout and in --out (default
-profiles/view_gate_step.json).  No GPU, no number.
+on what the matrices say).  --rule rate times args.pseudoRule = "rate" (--sel-rate) instead: per
+pseudo-loss call two ubpl_softmax_peak_scores reads (the student's stacks, the teachers' last
+stacks), two ubpl_rank_threshold launches and ubpl_loss_finalize_ranked in ubpl_loss_finalize's
+place.  One JSON line on stdout and in --out (default profiles/view_gate_step.json, for --rule
+rate profiles/rate_rule_step.json).  No GPU, no number.
 
-    python tools/view_gate_bench.py [--steps 10] [--repeats 5] [--dist-thr 4] [--out FILE]
+    python tools/view_gate_bench.py [--rule uncertainty|rate] [--steps 10] [--repeats 5] [--dist-thr 4]
+                                    [--sel-rate 0.5] [--out FILE]
 """
 import argparse
 import json
@@ -45,9 +50,13 @@ def main():
     ap.add_argument("--steps", type=int, default=10, help="timed steps per variant per round")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--rule", choices=("uncertainty", "rate"), default="uncertainty")
     ap.add_argument("--dist-thr", type=float, default=4.0)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "view_gate_step.json"))
+    ap.add_argument("--sel-rate", type=float, default=0.5)
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "rate_rule_step.json" if a.rule == "rate" else "view_gate_step.json")
 
     import bench
     from ubpl_amd import _lib, kernels as Kn
@@ -76,7 +85,12 @@ def main():
     args_off.nStack, args_off.outRes = S, res // 4
     args_on = bench.make_args(B)
     args_on.nStack, args_on.outRes = S, res // 4
-    args_on.pseudoRule, args_on.distThrMax = "uncertainty", a.dist_thr
+    if a.rule == "rate":
+        args_on.pseudoRule, args_on.pseudoSelRate = "rate", a.sel_rate
+        rule_on = {"pseudoRule": "rate", "pseudoSelRate": a.sel_rate}
+    else:
+        args_on.pseudoRule, args_on.distThrMax = "uncertainty", a.dist_thr
+        rule_on = {"pseudoRule": "uncertainty", "distThrMax": a.dist_thr, "pseudoRefine": "taylor"}
 
     def run(on, n):
         """n steps of one variant after two untimed ones (which re-capture the step) -> ms per step."""
@@ -108,7 +122,7 @@ def main():
     row["delta_rel"] = round(row["delta_ms"] / row["off_ms"], 5)
     row["outside_spread"] = bool(abs(row["delta_rel"]) > max(row["off_spread"], row["on_spread"]))
     out = {"tool": "view_gate_bench", "workload": "MT_UBPL train step, HG%d, K=%d, %dx%d, B=%d" % (S, K, res, res, B),
-           "rule_on": {"pseudoRule": "uncertainty", "distThrMax": a.dist_thr, "pseudoRefine": "taylor"},
+           "rule_on": rule_on,
            "captured": captured, "steps_per_round": a.steps, "repeats": a.repeats,
            "precision": Kn.conv_precision_name(), "device": torch.cuda.get_device_name(0),
            "images_per_sec": {"off": round(B / row["off_ms"] * 1e3, 2), "on": round(B / row["on_ms"] * 1e3, 2)}}

@@ -118,6 +118,79 @@ def row_grad(g, w, gscale, extra, da, accumulate=False):
     return da
 
 
+# ------------------------------------------------------------------ L2b-L2d (rank / softmax-score selection)
+MAX_SCORE_MAPS = 32        # ubpl_softmax_peak_scores: K maps of a pixel in registers
+MAX_SCORE_MEMBERS = 8
+MAX_RANK_GROUP = 8192      # ubpl_rank_threshold: one group in LDS
+
+
+def softmax_peak_scores(x, x_sb, x_ss, x_sm, M, B, S, K, HW, out=None):
+    """score [B*S*K] of the maps (b,s,k) = mean over m < M of x + m*x_sm + b*x_sb + s*x_ss + k*HW
+    (x: a flat view at the base element): softmax across the K maps at every pixel, then the
+    per-map maximum (utils/losses.py:137-138)."""
+    _chk(x, "x")
+    if not 1 <= K <= MAX_SCORE_MAPS or not 1 <= M <= MAX_SCORE_MEMBERS:
+        raise ValueError("ubpl_amd: softmax_peak_scores takes 1..%d maps and 1..%d members, got %d and %d"
+                         % (MAX_SCORE_MAPS, MAX_SCORE_MEMBERS, K, M))
+    score = torch.empty(B * S * K, device=x.device, dtype=F32) if out is None else out
+    call("ubpl_softmax_peak_scores", x, int(x_sb), int(x_ss), int(x_sm), M, B, S, K, HW, score)
+    return score
+
+
+def rank_threshold(scores, G, N, rank, out=None):
+    """thr [G]: the rank-th smallest (0-based) of each group of N in scores [G*N], on the device."""
+    _chk(scores, "scores")
+    if not 1 <= N <= MAX_RANK_GROUP:
+        raise ValueError("ubpl_amd: rank_threshold takes groups of 1..%d scores, got %d" % (MAX_RANK_GROUP, N))
+    if not 0 <= rank < N:
+        raise IndexError("ubpl_amd: rank %d is out of range for a group of %d scores" % (rank, N))
+    thr = torch.empty(G, device=scores.device, dtype=F32) if out is None else out
+    call("ubpl_rank_threshold", scores, G, N, int(rank), thr)
+    return thr
+
+
+def loss_finalize_ranked(kind, sq, ascore, tscore, athr, tthr, gate, sw, use_gate, use_sw, B, S, K,
+                         want_score=True, out=None):
+    """loss_finalize for kinds 1 and 2 with given scores and per-stack device thresholds
+    -> (sum [1], cnt [4] int32, score [K] or None, w [B*S*K])."""
+    dev = sq.device
+    if kind not in (1, 2):
+        raise ValueError("ubpl_amd: loss_finalize_ranked is kind 1 or 2, got %r" % (kind,))
+    if tscore is None or tthr is None or (kind == 2 and (ascore is None or athr is None)):
+        raise ValueError("ubpl_amd: loss_finalize_ranked kind %d needs its scores and thresholds" % kind)
+    out_sum, out_cnt, score, w = out if out is not None else (None,) * 4
+    out_sum = torch.empty(1, device=dev, dtype=F32) if out_sum is None else out_sum
+    out_cnt = torch.empty(4, device=dev, dtype=torch.int32) if out_cnt is None else out_cnt
+    if score is None and want_score:
+        score = torch.empty(K, device=dev, dtype=F32)
+    w = torch.empty(B * S * K, device=dev, dtype=F32) if w is None else w
+    call("ubpl_loss_finalize_ranked", int(kind), sq, ascore, tscore, athr, tthr, gate, sw, int(use_gate), int(use_sw),
+         B, S, K, out_sum, out_cnt, score, w)
+    return out_sum, out_cnt, score, w
+
+
+def loss_finalize_rank(kind, sq, ascore, tscore, t_stacks, rank, gate, sw, use_gate, use_sw, B, S, K, want_score=True):
+    """rank_threshold of every stack of both score sets and loss_finalize_ranked in one launch (the
+    training step's form).  tscore [B,t_stacks,K] with t_stacks S, or 1: one target score per (b,k)
+    for every stack -> (sum [1], cnt [4] int32, score [K] or None, w [B*S*K], thr [2*S]: rateThr1
+    [S] (NaN for kind 1), then rateThr2 [S])."""
+    dev = sq.device
+    if kind not in (1, 2):
+        raise ValueError("ubpl_amd: loss_finalize_rank is kind 1 or 2, got %r" % (kind,))
+    if not 1 <= B * K <= MAX_RANK_GROUP:
+        raise ValueError("ubpl_amd: loss_finalize_rank ranks 1..%d scores per stack, got %d" % (MAX_RANK_GROUP, B * K))
+    if not 0 <= rank < B * K:
+        raise IndexError("ubpl_amd: rank %d is out of range for %d scores" % (rank, B * K))
+    out_sum = torch.empty(1, device=dev, dtype=F32)
+    out_cnt = torch.empty(4, device=dev, dtype=torch.int32)
+    score = torch.empty(K, device=dev, dtype=F32) if want_score else None
+    w = torch.empty(B * S * K, device=dev, dtype=F32)
+    thr = torch.empty(2 * S, device=dev, dtype=F32)
+    call("ubpl_loss_finalize_rank", int(kind), sq, ascore, tscore, int(t_stacks), int(rank), gate, sw, int(use_gate),
+         int(use_sw), B, S, K, thr, out_sum, out_cnt, score, w)
+    return out_sum, out_cnt, score, w, thr
+
+
 # ------------------------------------------------------------------ L5
 def fdl_cov_forward(f1, f2, rowmask=None):
     _chk(f1, "f1")

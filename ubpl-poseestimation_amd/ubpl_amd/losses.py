@@ -186,6 +186,142 @@ class JointPseudoLoss3(nn.Module):
         return s, c[1], c[2], score, self.scoreThr, self.scoreThr
 
 
+def sel_rank(n, selRate):
+    """The reference's index into the sorted scores, in its own Python-float arithmetic
+    (utils/losses.py:139): not exact — int(10 * (1 - 0.9)) is 0."""
+    return int(n * (1 - selRate))
+
+
+class _RankedRowLoss(torch.autograd.Function):
+    """_RowLoss with the reference's softmax scores in the mask (utils/losses.py:73-166, 213-243).
+    spec = (kind, S, K, HW, tg, use_gate, use_sw, sel): tg as _RowLoss's; sel = ("rank", r): per
+    stack the r-th smallest of the batch's B*K scores is the threshold (folded into the finalize
+    launch, ubpl_loss_finalize_rank), or ("thr", v): the constant v.  kind 2 masks by the scores of
+    both inputs, kind 1 by the second's.  A target that is one map per row for all stacks
+    (t_ss == 0) is scored once.
+    forward: (sum, cnt[4] int32, score[K], thr[2*S]: rateThr1[S] then rateThr2[S]) on the device,
+    no host sync."""
+
+    @staticmethod
+    def forward(ctx, a, t, spec, gate, sw):
+        kind, S, K, HW, tg, use_gate, use_sw, sel = spec
+        B = a.shape[0]
+        g = _geom(a, S, K, HW, t, *tg)
+        sq, _, _ = Kn.row_stats(g)
+        t_sb, t_ss, t_sm, M = tg[:4]
+        St = 1 if t_ss == 0 else S
+        tsc = Kn.softmax_peak_scores(g.t_ptr, t_sb, t_ss, t_sm, M, B, St, K, HW)
+        asc = Kn.softmax_peak_scores(a, S * K * HW, K * HW, 0, 1, B, S, K, HW) if kind == 2 else None
+        if sel[0] == "rank":
+            s, cnt, score, w, thr = Kn.loss_finalize_rank(kind, sq, asc, tsc, St, sel[1], gate, sw, use_gate, use_sw,
+                                                          B, S, K, want_score=(kind == 2))
+        else:
+            thr = torch.full((2 * S,), float(sel[1]), device=a.device, dtype=torch.float32)
+            if St != S:                                      # the one target score per (b,k) serves every stack
+                tsc = tsc.view(B, 1, K).expand(B, S, K).contiguous().view(-1)
+            s, cnt, score, w = Kn.loss_finalize_ranked(kind, sq, asc, tsc, thr[:S] if kind == 2 else None, thr[S:],
+                                                       gate, sw, use_gate, use_sw, B, S, K, want_score=(kind == 2))
+        ctx.save_for_backward(a, t, w)
+        ctx.spec = spec
+        ctx.t_grad = t.requires_grad and tg[3] == 1 and tg[2] == 0
+        outs = (s.view(()), cnt, score if score is not None else s.new_empty(0), thr)
+        ctx.mark_non_differentiable(*outs[1:])
+        return outs
+
+    @staticmethod
+    def backward(ctx, gs, *_):
+        a, t, w = ctx.saved_tensors
+        _, S, K, HW, tg = ctx.spec[:5]
+        g = _geom(a, S, K, HW, t, *tg)
+        da = torch.empty_like(a)
+        Kn.row_grad(g, w, gs.reshape(1).contiguous().float(), 2.0 / HW, da)
+        dt = -da if ctx.t_grad else None
+        return da, dt, None, None, None
+
+
+def _ens_geom(t, nstack, B, K, HW):
+    """Target strides of an ensemble stack [M,B,(St,)K,R,R]: the mean over M of the last stack."""
+    M = t.shape[0]
+    if nstack == 1:
+        return (K * HW, 0, t.numel() // M, M, 0)
+    St = t.shape[2]
+    return (St * K * HW, 0, B * St * K * HW, M, (St - 1) * K * HW)
+
+
+def _pseudo_ranked(mod, preds, targets, sampleWeight, sel):
+    _lib.require_gpu(preds)
+    a = preds.contiguous()
+    B, S, K, HW = _rows_of(a, mod.nStack)
+    t = targets.detach().contiguous()
+    sw = _sw_vec(sampleWeight)
+    spec = (2, S, K, HW, _ens_geom(t, mod.nStack, B, K, HW), False, True, sel)
+    s, cnt, score, thr = _RankedRowLoss.apply(a, t, spec, None, sw)
+    c = cnt.tolist()
+    if c[3] == 0:
+        raise RuntimeError("stack expects a non-empty TensorList")  # utils/losses.py:107,157
+    return s, c[1], c[2], score, thr[:S], thr[S:]
+
+
+class JointPseudoLoss(nn.Module):
+    """utils/losses.py:73-115: JointPseudoLoss3's mask on the softmax scores (softmax across the
+    keypoint axis at every pixel, then the per-map maximum) at the constant scoreThr.  Returns
+    (sum, n_pseudo, n_sel, score[K]).  For maps in [0,1] and K = 16 a softmax score cannot exceed
+    e/(e+15) = 0.153: the default 0.8 selects nothing, as in the reference."""
+
+    def __init__(self, nStack=1, scoreThr=0.8):
+        super().__init__()
+        self.nStack, self.scoreThr = nStack, scoreThr
+
+    def forward(self, preds, targets, sampleWeight):
+        return _pseudo_ranked(self, preds, targets, sampleWeight, ("thr", float(self.scoreThr)))[:4]
+
+
+class JointPseudoLoss2(nn.Module):
+    """utils/losses.py:118-166: the pseudo-label loss that keeps a fixed SHARE of the joints.  Per
+    stack, the threshold of each input is the int(B*K*(1 - selRate))-th smallest of its B*K softmax
+    scores (sel_rank: the reference's float expression), and a row counts where both inputs'
+    scores reach their thresholds.  The ranking is over every row of the batch, labeled rows
+    (sampleWeight 0) included, as the reference ranks them.  Ties at the threshold are all kept.
+    Returns (sum, n_pseudo, n_sel, score[K], rateThr1[S], rateThr2[S]); the thresholds are device
+    tensors.  selRate <= 0 raises IndexError as the reference's indexing does; no row with
+    sampleWeight > 0 raises RuntimeError."""
+
+    def __init__(self, nStack=1, selRate=0.5):
+        super().__init__()
+        self.nStack, self.selRate = nStack, selRate
+
+    def forward(self, preds, targets, sampleWeight):
+        B, _, K, _ = _rows_of(preds, self.nStack)
+        rank = sel_rank(B * K, self.selRate)
+        if not 0 <= rank < B * K:
+            raise IndexError("index %d is out of bounds for dimension 0 with size %d" % (rank, B * K))
+        return _pseudo_ranked(self, preds, targets, sampleWeight, ("rank", rank))
+
+
+class JointDistLoss_mt(nn.Module):
+    """utils/losses.py:213-243: consistency kept where the second input's per-stack softmax score
+    reaches the int(B*K*(1 - selRate))-th smallest of its batch.  Returns (sum, nStack*#gate)."""
+
+    def __init__(self, nStack=1, useKPsGate=False, useSampleWeight=False, selRate=0.5):
+        super().__init__()
+        self.nStack, self.useKPsGate, self.useSampleWeight, self.selRate = nStack, useKPsGate, useSampleWeight, selRate
+
+    def forward(self, preds1, preds2, kpsGate=None, sampleWeight=None):
+        _lib.require_gpu(preds1)
+        a = preds1.contiguous()
+        B, S, K, HW = _rows_of(a, self.nStack)
+        rank = sel_rank(B * K, self.selRate)
+        if not 0 <= rank < B * K:
+            raise IndexError("index %d is out of bounds for dimension 0 with size %d" % (rank, B * K))
+        t = preds2.contiguous()
+        gate = _f32c(kpsGate)
+        sw = _sw_vec(sampleWeight)
+        spec = (1, S, K, HW, (S * K * HW, K * HW, 0, 1), bool(self.useKPsGate and gate is not None),
+                bool(self.useSampleWeight and sw is not None), ("rank", rank))
+        s, cnt, _, _ = _RankedRowLoss.apply(a, t, spec, gate, sw)
+        return s, int(cnt[0].item())
+
+
 class JointFeatureDistLoss(nn.Module):
     """utils/losses.py:56-70 (FDL_type 'distance')."""
 

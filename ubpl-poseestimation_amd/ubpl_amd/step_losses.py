@@ -4,7 +4,7 @@ section of each train.py step (between the networks' forwards and the backward)
 builds its sums, counts and FDL views from these; _RecordLayout says where they go."""
 import torch
 
-from .losses import _RowLoss, features_cov
+from .losses import _RankedRowLoss, _RowLoss, features_cov
 from .process import render_batch
 
 
@@ -75,6 +75,18 @@ def _pseudo_gated(preds, targets, sw, S, thr, gate):
         raise ValueError("ubpl_amd: _pseudo_gated takes a gate of [B,K] = %d x %d entries" % (B, K))
     spec = (3, S, K, HW, (St * K * HW, 0, B * St * K * HW, M, (St - 1) * K * HW), False, True, float(thr))
     return _RowLoss.apply(preds, targets, spec, gate, sw)
+
+
+def _pseudo_ranked(preds, targets, sw, S, rank):
+    """JointPseudoLoss2(nStack=S) with targets [M,B,S,K,R,R] in _pseudo's place: the row mask is
+    each input's softmax score >= the rank-th smallest of the batch's B*K (rank a host integer,
+    losses.sel_rank) -> (sum, cnt[4], score[K], thr[2*S]: rateThr1[S] then rateThr2[S]), all on the
+    device; the rank selections run inside the finalize launch (ubpl_loss_finalize_rank)."""
+    B, K = preds.shape[0], preds.shape[2]
+    HW = preds.shape[-1] * preds.shape[-2]
+    M, St = targets.shape[0], targets.shape[2]
+    spec = (2, S, K, HW, (St * K * HW, 0, B * St * K * HW, M, (St - 1) * K * HW), False, True, ("rank", int(rank)))
+    return _RankedRowLoss.apply(preds, targets, spec, None, sw)
 
 
 def _norm(s, n):
@@ -175,15 +187,18 @@ class _RecordLayout:
       sums (local / all-reduced): per model SUMS, then one per FDL view
       counts:                     per model `counts`, then one per FDL view
       packed (the one device->host copy): [3M+1 records: per model RECS, then fdc | counts | `blocks` x K scores]
+                                          and, only with rate_thr (the "rate" pseudo rule): [| per model rateThr1, rateThr2]
     A plain host object (no tensors): built when the step is captured and reused at every replay."""
     SUMS = ("mtc", "pec", "epc")
     RECS = ("pec", "mtc", "epc")
 
-    def __init__(self, M, counts, nfd, K, blocks=1):
+    def __init__(self, M, counts, nfd, K, blocks=1, rate_thr=False):
         self.M, self.counts, self.nfd, self.K = M, tuple(counts), nfd, K
         nc = len(self.counts) * M
         self.nrec, self.ncn = 3 * M + 1, nc + nfd
         self.size = self.nrec + self.ncn + blocks * K
+        self.rate_thr = slice(self.size, self.size + 2 * M) if rate_thr else None     # in packed
+        self.size = self.rate_thr.stop if rate_thr else self.size
         self.fdc = 3 * M                                              # in packed: the FDL record
         self.fdl_sums = slice(3 * M, 3 * M + nfd)                     # in sums: the FDL views
         self.fdl_counts = slice(nc, nc + nfd)                         # in counts

@@ -33,13 +33,13 @@ import torch
 from . import dist as D
 from . import view_gate as VG
 from .guard import _configure_guard, _gd, _guard_and_restore, _guard_nets, _save_stats, _SkipWatch
-from .losses import AvgCounter
+from .losses import AvgCounter, sel_rank
 from .parameters import ema_alpha, update_ema_variables
 from .process import render_batch
 from .step_graph import _collective, _drive, _LaggedRecords, _StepGraph  # noqa: F401
 from .step_losses import (_dist_last, _dist_mt2_last, _fdl_record, _fdl_record_sums, _fdl_rows,  # noqa: F401
                           _fdl_total, _fdl_view, _islabeled, _mse, _mse_plain, _norm, _pseudo, _pseudo_gated,
-                          _RecordLayout, _targets, _w)
+                          _pseudo_ranked, _RecordLayout, _targets, _w)
 from .streams import _backward_all, _join_merge, _ModelStreams, _OnMain, _PhaseCheck  # noqa: F401
 from .validation import fold_valid_rows, gather_valid_rows, valid_batch_row, validate  # noqa: F401
 
@@ -141,12 +141,16 @@ def _pseudo_rate(n_sel, n_ps, guarded=False):
     return int(n_sel) / int(n_ps)
 
 
-def _pseudo_line(bat, kind, args, rate, n_sel, n_ps, scores, dist_thr=None):
-    """dist_thr: the view-consistency rule's threshold, shown only when that rule is on."""
+def _pseudo_line(bat, kind, args, rate, n_sel, n_ps, scores, dist_thr=None, sel_rate=None, rate_thr=()):
+    """dist_thr: the view-consistency rule's threshold, shown only when that rule is on.
+    sel_rate, rate_thr: the "rate" rule's share and the step's thresholds (per model rateThr1,
+    rateThr2), shown only when that rule is on."""
     thr = format(args.pseudoScoreThr, ".2f") + ("" if dist_thr is None else " distThr:" + format(dist_thr, ".2f"))
-    print("batch.{}{} (scoreThr:{}): {} ({}/{}), pseudo-score: [{}]".format(
+    thr += "" if sel_rate is None else " selRate:" + format(sel_rate, ".2f")
+    tail = "" if sel_rate is None else ", rateThr: [{}]".format(", ".join(format(v, ".4f") for v in rate_thr))
+    print("batch.{}{} (scoreThr:{}): {} ({}/{}), pseudo-score: [{}]{}".format(
         format(bat + 1, "5d"), kind, thr, format(rate, ".2f"),
-        format(n_sel, "5d"), format(n_ps, "5d"), ", ".join(format(v, ".3f") for v in scores)))
+        format(n_sel, "5d"), format(n_ps, "5d"), ", ".join(format(v, ".3f") for v in scores), tail))
 
 
 # ---------------------------------------------------------------------------
@@ -167,6 +171,7 @@ def _mt_ubpl_core(models, models_ema, optims, args, augs_imgMap, augs_heatmaps, 
     use_ep = getattr(args, "useEnsemblePseudo", True)        # :271 (False: epc = 0, no print)
     rule = VG.options(args)                              # the view-consistency rule (off: the score rule)
     gated = rule.on and use_ep
+    ranked = rule.sel_rate is not None and use_ep        # the "rate" rule: JointPseudoLoss2 for JointPseudoLoss3
     if gated:
         VG.check_batch(rule, meta, A, M)                     # ValueError before any launch
     for o in optims:
@@ -215,15 +220,21 @@ def _mt_ubpl_core(models, models_ema, optims, args, augs_imgMap, augs_heatmaps, 
             tgs = [torch.stack([outs_ema[j][a] for j in range(M)]) for a in range(A)]
             gate = VG.view_gate(rule, tgs, meta["viewmat"], imgs[0].shape[-1])
     # ---- loss sums / counts on device
-    sums, ps_scores = [], []
+    sums, ps_scores, rate_thrs = [], [], []
+    rank = sel_rank(B * K, rule.sel_rate) if ranked else None     # a host integer: B and K are static
     for mi in range(M):
-        ms = []
+        ms, thr_m = [], []
         for a in range(A):
             s_d, _ = _dist_last(outs[mi][a], outs_ema[mi][a])
             s_p, c_p = _mse(outs[mi][a], hms[a], S, gates[a], sw.reshape(-1, 1))
             if gated:
                 s_e, c_e, sc_e = _pseudo_gated(outs[mi][a], tgs[a], nega, S, rule.thr, gate)
                 ps_scores.append(sc_e)
+            elif ranked:
+                tg = torch.stack([outs_ema[j][a] for j in range(M)])
+                s_e, c_e, sc_e, thr = _pseudo_ranked(outs[mi][a], tg, nega, S, rank)
+                ps_scores.append(sc_e)
+                thr_m.append(thr)                            # rateThr1 [S], rateThr2 [S]
             elif use_ep:
                 tg = torch.stack([outs_ema[j][a] for j in range(M)])
                 s_e, c_e, sc_e = _pseudo(outs[mi][a], tg, nega, S, args.pseudoScoreThr)
@@ -232,6 +243,7 @@ def _mt_ubpl_core(models, models_ema, optims, args, augs_imgMap, augs_heatmaps, 
                 s_e, c_e = zero, zcnt
             ms.append((s_d, s_p, c_p, s_e, c_e))
         sums.append(ms)
+        rate_thrs += thr_m
     fd = []
     if args.FDLWeight > 0:
         rowmask = _fdl_rows(sw, args)
@@ -241,7 +253,7 @@ def _mt_ubpl_core(models, models_ema, optims, args, augs_imgMap, augs_heatmaps, 
     per = [{"mtc": sum(x[0] for x in ms), "pec": sum(x[1] for x in ms), "epc": sum(x[3] for x in ms),
             "pec_n": sum(x[2][0] for x in ms), "epc_n": sum(x[4][1] for x in ms), "n_sel": sum(x[4][2] for x in ms)}
            for ms in sums]
-    L = _RecordLayout(M, _MT_UBPL_COUNTS, len(fd), K)
+    L = _RecordLayout(M, _MT_UBPL_COUNTS, len(fd), K, rate_thr=ranked)
     loc = [p[n] for p in per for n in L.SUMS] + _fdl_record_sums(fd)
     cn = [p[n] for p in per for n in L.counts] + [n[0] for _, _, n in fd]
     counts = torch.stack([c.float() for c in cn])
@@ -268,7 +280,10 @@ def _mt_ubpl_core(models, models_ema, optims, args, augs_imgMap, augs_heatmaps, 
         g_rec += [r[n] for n in L.RECS]
     g_rec.append(_fdl_record(fd, gsums[L.fdl_sums], gcounts[L.fdl_counts], W, args.FDLWeight) if fd else zero)
     score = torch.stack(ps_scores).mean(0) if use_ep else torch.zeros(K, device=dev)
-    return torch.cat([torch.stack([r.float() for r in g_rec]), gcounts, score]), L, mtc_n, B, use_ep
+    blocks = [torch.stack([r.float() for r in g_rec]), gcounts, score]
+    if ranked:                                               # per model: the mean over views and stacks of each
+        blocks.append(torch.stack(rate_thrs).view(M, A, 2, S).mean((1, 3)).reshape(-1))
+    return torch.cat(blocks), L, mtc_n, B, use_ep
 
 
 def _mt_ubpl_records(host, bat, L, mtc_n, B, use_ep, counters, args, verbose, guarded=False):
@@ -292,7 +307,8 @@ def _mt_ubpl_records(host, bat, L, mtc_n, B, use_ep, counters, args, verbose, gu
         rate = _pseudo_rate(n_sel, n_ps, guarded)
         if verbose:
             rule = VG.options(args)
-            _pseudo_line(bat, "", args, rate, n_sel, n_ps, host[L.scores()], rule.dist_thr if rule.on else None)
+            _pseudo_line(bat, "", args, rate, n_sel, n_ps, host[L.scores()], rule.dist_thr if rule.on else None,
+                         rule.sel_rate if L.rate_thr else None, host[L.rate_thr] if L.rate_thr else ())
 
 
 def train_mt_ubpl(trainLoader, models, models_ema, optims, args, verbose=True, pseudo_counts=None):
@@ -301,8 +317,12 @@ def train_mt_ubpl(trainLoader, models, models_ema, optims, args, verbose=True, p
     batch shapes repeat (UBPL_STEP_GRAPH=0: every step eager).
     args.pseudoRule "uncertainty" / "score+uncertainty" (with args.distThrMax; pseudoRefine,
     pseudoBlurSigma) selects the pseudo labels by the view-consistency rule (view_gate.py); the
-    batches then carry meta["viewmat"].  pseudo_counts: a dict that receives the epoch's totals of
-    the steps' pseudo-label counts, "n_pseudo" and "n_sel" (what the active rule selected)."""
+    batches then carry meta["viewmat"].  args.pseudoRule "rate" (with args.pseudoSelRate in (0, 1])
+    keeps that share of every batch's joints, ranked by softmax score: JointPseudoLoss2 in
+    JointPseudoLoss3's place ("Rank-based pseudo-label selection").  pseudo_counts: a
+    dict that receives the epoch's totals of the steps' pseudo-label counts, "n_pseudo" and "n_sel"
+    (what the active rule selected), and under the "rate" rule "steps" and the sums over the steps of
+    the models' mean thresholds, "rate_thr1" and "rate_thr2"."""
     rule = VG.options(args)
     if rule.on:
         VG.constants(rule, models[0].flat_params.device)     # host -> device, ahead of any capture
@@ -311,6 +331,11 @@ def train_mt_ubpl(trainLoader, models, models_ema, optims, args, verbose=True, p
         if pseudo_counts is not None and use_ep:             # the step's own counts, summed over the epoch
             pseudo_counts["n_sel"] = pseudo_counts.get("n_sel", 0) + L.total(host, "n_sel")
             pseudo_counts["n_pseudo"] = pseudo_counts.get("n_pseudo", 0) + L.total(host, "epc_n")
+            if L.rate_thr:
+                t = host[L.rate_thr]
+                pseudo_counts["steps"] = pseudo_counts.get("steps", 0) + 1
+                pseudo_counts["rate_thr1"] = pseudo_counts.get("rate_thr1", 0.) + sum(t[0::2]) / L.M
+                pseudo_counts["rate_thr2"] = pseudo_counts.get("rate_thr2", 0.) + sum(t[1::2]) / L.M
         return _mt_ubpl_records(host, bat, L, mtc_n, B, use_ep, *rest)
     return _train_steps(_mt_ubpl_core, records, trainLoader, models, models_ema, optims, args, verbose)
 
@@ -484,6 +509,7 @@ def train_mt(trainLoader, model, model_ema, optim, args):
 
 def train_supervised(trainLoader, model, optim, args):
     """projects/supervised.py:135-175 -> pec_avg."""
+    VG.refuse(args, "train_supervised")
     pec_c = AvgCounter()
     dev = model.flat_params.device
     model.train()

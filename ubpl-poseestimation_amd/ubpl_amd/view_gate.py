@@ -7,24 +7,41 @@ The step runs every sample as A augmented views through both teachers.  With arg
 folded by ubpl_view_uncertainty_samples — the reference's pseudo_cal_unc (utils/business.py:
 220-234), which it wrote for training and wired into no project — into gate [B,K]: 1 where every
 teacher's peaks agree across the views and with the other teachers within args.distThrMax pixels.
-The gate then masks the ensemble-pseudo loss (step_losses._pseudo_gated)."""
+The gate then masks the ensemble-pseudo loss (step_losses._pseudo_gated).
+
+RULES is the one list of the step's pseudo-label rules, so the "rate" rule (rank-based selection,
+step_losses._pseudo_ranked) has its option check here too; it needs no gate and no constants."""
 import torch
 
 from . import kernels as Kn
 from . import predict_args as PA
 
-RULES = ("score", "uncertainty", "score+uncertainty")
+RULES = ("score", "uncertainty", "score+uncertainty", "rate")
+
+
+def check_sel_rate(rule, value):
+    """args.pseudoSelRate of the "rate" rule ("Rank-based pseudo-label selection"): the
+    share of the batch's joints the ensemble-pseudo term keeps, a float in (0, 1]; required, no default."""
+    if value is None:
+        raise ValueError("ubpl_amd: pseudoRule %r needs pseudoSelRate, the share of joints kept, in (0, 1]" % rule)
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not 0.0 < value <= 1.0:
+        raise ValueError("ubpl_amd: pseudoSelRate is a float in (0, 1], got %r" % (value,))
+    return float(value)
 
 
 class GateOptions:
     """The rule's options read from a step's args, checked on the host: every existing namespace
-    (none of the four attributes) is the score rule, `on` False."""
+    (none of the four attributes) is the score rule, `on` False.  `on` is the view-consistency
+    gate; the "rate" rule (sel_rate not None) selects by rank instead and is not combined with it."""
 
     def __init__(self, args):
         self.rule = getattr(args, "pseudoRule", "score")
         if self.rule not in RULES:
             raise ValueError("ubpl_amd: pseudoRule is one of %s, got %r" % (", ".join(RULES), self.rule))
-        self.on = self.rule != "score"
+        self.sel_rate = None                                 # the "rate" rule's share of joints kept
+        if self.rule == "rate":
+            self.sel_rate = check_sel_rate(self.rule, getattr(args, "pseudoSelRate", None))
+        self.on = self.rule not in ("score", "rate")
         if not self.on:
             return
         # the reference's name, and like the reference no default (predict_args.check_dist_thr)
@@ -50,7 +67,7 @@ def options(args):
     keeps them alive.  An entry is a few floats, one per option set a process ever trains with."""
     key = (getattr(args, "pseudoRule", "score"), getattr(args, "distThrMax", None),
            getattr(args, "pseudoRefine", None), getattr(args, "pseudoBlurSigma", None),
-           getattr(args, "pseudoScoreThr", None))
+           getattr(args, "pseudoScoreThr", None), getattr(args, "pseudoSelRate", None))
     try:
         opts = _OPTIONS.get(key)
     except TypeError:                                        # an unhashable value: let the checks name it
@@ -62,7 +79,8 @@ def options(args):
 
 def refuse(args, where):
     """The steps the rule is not wired into say so instead of ignoring the option."""
-    if options(args).on:
+    opts = options(args)
+    if opts.on or opts.sel_rate is not None:
         raise ValueError("ubpl_amd: pseudoRule %r is built into train_mt_ubpl only, not %s"
                          % (args.pseudoRule, where))
 
