@@ -214,6 +214,42 @@ def test_param_table_matches_reference_names():
     assert (live, dead) == (6570400, 1858688)      # grad-carrying vs unused skip params
 
 
+def test_hourglass_split_keeps_names_and_weight_table_invariant():
+    """ubpl_amd.hourglass, split into hourglass / hourglass_exec / hourglass_params, still
+    exposes its public names without a GPU; and the weight tables of build_table(16, 2),
+    built on the CPU for each conv precision, keep what build_weight_tables' docstring
+    states: per mode, a 3x3 conv is on the split tables or in ("rest", mode), never both,
+    and the split tables with ("rest", mode) cover every live conv weight that needs a
+    re-layout (= the f32 table wlay[mode])."""
+    from ubpl_amd import hourglass, kernels as Kn
+    from ubpl_amd.hourglass_params import build_weight_tables
+    for name in ("StackedHourglass", "pose_model", "PoseModel", "hg", "build_table", "BN_EPS", "BN_MOMENTUM",
+                 "_HourglassFn"):
+        assert hasattr(hourglass, name), name
+    tab = hourglass.build_table(16, 2)
+    offs, o = {}, 0
+    for name, shape, _, _ in tab:
+        offs[name] = (o, int(np.prod(shape)), shape)
+        o += (offs[name][1] + 3) // 4 * 4
+    ks = {name: shape[2] for name, shape, kind, _ in tab if kind == "cw"}
+    stem = "pre.0.conv.weight"
+    for prec in ("f32", "6xbf16", "2xfp16", "bf16"):
+        pieces = Kn.conv_precision_pieces(prec)
+        bwd = Kn.backward_pieces(pieces)
+        for bwd3 in {bwd, 2 if pieces == 2 else bwd}:          # (UBPL_FP16_BWD3 off and on)
+            wsp, wlay = build_weight_tables(tab, offs, "cpu", pieces, bwd, bwd3)
+            for mode in (0, 1):
+                split = [nm for sub in wsp[mode] for nm in sub[2]]
+                assert len(split) == len(set(split)), (prec, mode)     # one table per conv
+                rest = set(wlay[("rest", mode)][2])
+                assert not {nm for nm in set(split) & rest if ks[nm] == 3}, (prec, mode)
+                need = {name for name, shape, kind, live in tab if kind == "cw" and live
+                        and (shape[2] > 1 if mode == 0 else name != stem)}
+                assert set(wlay[mode][2]) == need, (prec, mode)
+                assert need <= set(split) | rest, (prec, mode, sorted(need - set(split) - rest)[:4])
+                assert bool(split) == bool(pieces), (prec, mode)
+
+
 def test_tools_weights_cpu():
     from types import SimpleNamespace
     from ubpl_amd.tools import ProjectTools

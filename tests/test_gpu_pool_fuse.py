@@ -232,8 +232,8 @@ def test_bn_backward_pool_vs_three_launches(shape):
 
 
 def _model_run(fuse, monkeypatch, imgs, dpreds):
-    from ubpl_amd import hourglass as HG
-    monkeypatch.setattr(HG, "_POOL_FUSE", fuse)
+    from ubpl_amd import hourglass as HG, hourglass_exec
+    monkeypatch.setattr(hourglass_exec, "_POOL_FUSE", fuse)      # (the executor's module reads the flag)
     torch.manual_seed(0)
     model = HG.StackedHourglass(16, 2, "default")
     model.train()

@@ -11,8 +11,7 @@ repeat, which (network, view) outputs differ from the first repeat.
          save for backward, as the students'), FWD_SYNC=1 (synchronize between
          networks: no overlap), FWD_KEEPALL=1 (every tensor an op allocates kept
          alive until the repeat ends: no memory block reused inside a repeat),
-         =2 (kept for the whole run: no block ever reused), UBPL_RELAYOUT_ONCE=1
-         (hourglass.py: the weight re-layouts only in each model's first forward),
+         =2 (kept for the whole run: no block ever reused),
          FWD_LOCATE=1 (forwards that save for backward; every saved activation of
          every (network, view) compared with the first repeat's, in execution
          order: names the first layer whose output differs)
@@ -24,25 +23,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "ubpl-poseestimation_amd"), ROOT]
 
 import torch  # noqa: E402
-
-
-def analyse_add(r, n, v, k, up, low, out):
-    """out should be up + nearest-upsample(low); name what the wrong elements hold instead."""
-    lu = low.repeat_interleave(2, dim=2).repeat_interleave(2, dim=3)
-    want = up + lu
-    bad = (out != want).reshape(-1)
-    nb = int(bad.sum())
-    if nb == 0:
-        return
-    o, u, w, l2 = out.reshape(-1)[bad], up.reshape(-1)[bad], want.reshape(-1)[bad], lu.reshape(-1)[bad]
-    idx = bad.nonzero().reshape(-1)
-    # 4 floats per thread, 256 threads per block: block-sized chunks of the flat index
-    blk = torch.unique(idx // 1024)
-    print("   rep %d net%d/v%d %s: %d of %d wrong (%.2f%%); =up (add missing) %d, =up+2low (added twice) %d, "
-          "=0 %d; flat index %d..%d, %d distinct 1024-element chunks (first %s)" % (
-              r, n, v, k, nb, bad.numel(), 100.0 * nb / bad.numel(), int((o == u).sum()),
-              int((o == u + 2 * l2).sum()), int((o == 0).sum()), int(idx[0]), int(idx[-1]), blk.numel(),
-              blk[:6].tolist()), flush=True)
 
 
 def main():
@@ -120,11 +100,6 @@ def main():
             for n in range(nets):
                 for v in range(views):
                     shown = 0
-                    cd = dict(cur[n][v][1])
-                    for k, b in cur[n][v][1]:
-                        if k.endswith(".add_out[0]") and k.replace(".add_out[0]", ".add_in[0]") in cd:
-                            analyse_add(r, n, v, k, cd[k.replace(".add_out[0]", ".add_in[0]")],
-                                        cd[k.replace(".add_out[0]", ".add_in[1]")], b)
                     for (k, a), (_, b) in zip(ref[n][v][1], cur[n][v][1]):
                         if not torch.equal(a, b):
                             print("   rep %d net%d/v%d %s differing saved tensor: %s %s max |d| %.3g" % (
