@@ -3,7 +3,9 @@
 The exact-f32 MFMA path (conv_f32_fwd.hip, conv_f32_wgrad.hip) is the yardstick: on the same inputs the
 3-piece bf16 path (npieces=3, "6xbf16", exact operands) and the 2-piece fp16
 path (npieces=2, "2xfp16": operands to 2^-22, 3 products) must land within
-F16_BAR / 2x the f32 path's own error against float64.  Weight re-layout,
+F16_BAR / 2x the f32 path's own error against float64 — an error that is itself
+capped wherever it serves as a bar (f32_chain_ref.yardstick_cap: the f32 kernels
+are held to their chain in tests/test_gpu_f32_yardstick.py).  Weight re-layout,
 prologue, padding, residual, split-K and the data-gradient layout are all
 exercised.
 """
@@ -11,6 +13,8 @@ import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+from f32_chain_ref import yardstick_cap
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -98,6 +102,7 @@ def test_split_forward_and_dgrad_vs_f64(case, npieces):
     y_sp = Kn.conv2d_forward_split(d(x32), ws, d(b32), ps, ph, res=d(res32))
     e32, esp = _rel(y_f32, yref), _rel(y_sp, yref)
     print("fwd %s np=%d: f32 %.2e split %.2e" % (case, npieces, e32, esp))
+    yardstick_cap("split fwd %s" % (case,), e32, Cin * KS * KS)
     if npieces == 3:
         assert esp <= 2 * e32 + 1e-8, (esp, e32)
     else:
@@ -110,6 +115,7 @@ def test_split_forward_and_dgrad_vs_f64(case, npieces):
     dx_f32 = Kn.conv2d_dgrad(d(dy), d(w32))
     e32, esp = _rel(dx_f32, dxref), _rel(dx_sp, dxref)
     print("dgrad %s np=%d: f32 %.2e split %.2e" % (case, npieces, e32, esp))
+    yardstick_cap("split dgrad %s" % (case,), e32, Cout * KS * KS)
     if npieces == 3:
         assert esp <= 2 * e32 + 1e-8, (esp, e32)
     else:
@@ -160,6 +166,7 @@ def test_psa_forward_and_dgrad_vs_f64(case, npieces):
     d = lambda t: None if t is None else t.to(DEV)
     ps, ph = (d(sc32), d(sh32)) if pro else (None, None)
     y_f32 = Kn.conv2d_forward(d(x32), d(w32), d(b32), 1, ps, ph, res=d(res32))
+    yardstick_cap("psa fwd %s np=%d" % (case, npieces), _rel(y_f32, yref), Cin * KS * KS)
     for pad in sorted({(KS - 1) // 2, 1}):
         xs = Kn.split_activation(d(x32), npieces, pad, ps, ph)
         ws = Kn.conv_weight_split(d(w32), 0, npieces)
@@ -175,6 +182,7 @@ def test_psa_forward_and_dgrad_vs_f64(case, npieces):
     dx_f32 = Kn.conv2d_dgrad(d(dy), d(w32))
     e32, esp = _rel(dx_f32, dxref), _rel(dx_sp, dxref)
     print("psa dgrad %s np=%d: f32 %.2e split %.2e" % (case, npieces, e32, esp))
+    yardstick_cap("psa dgrad %s np=%d" % (case, npieces), e32, Cout * KS * KS)
     assert _ok(esp, e32, npieces), (esp, e32)
 
 
@@ -347,6 +355,7 @@ def test_wgrad3_psa_vs_f64(case):
     Kn.conv2d_wgrad(d(dy), d(x), 3, 1, dw32, db32, d(sc), d(sh), accumulate=False)
     e32, esp = _rel(dw32, dwref), _rel(dw - 0.25, dwref)
     print("wgrad3 %s: f32 %.2e split %.2e" % (case, e32, esp))
+    yardstick_cap("wgrad3 %s" % (case,), e32, B * H * W)
     assert esp <= 2 * e32 + 1e-8, (esp, e32)
     assert _rel(db + 0.5, dbref) <= 1e-5
 
@@ -453,6 +462,7 @@ def test_2xfp16_3x3_gradients_vs_f64(case):
     dx32 = Kn.conv2d_dgrad(dy, d(w))
     e32, e16 = _rel(dx32, dxref), _rel(dx, dxref)
     print("2xfp16 dgrad %s: f32 %.2e 2xfp16 %.2e" % (case, e32, e16))
+    yardstick_cap("2xfp16 dgrad %s" % (case,), e32, Cout * 9)
     assert _ok(e16, e32, 2), (e16, e32)
     # weight gradient from the forward's 2xfp16 image
     inp = F.relu((x.double() * sc.double()[None, :, None, None] + sh.double()[None, :, None, None]).float())
@@ -465,6 +475,7 @@ def test_2xfp16_3x3_gradients_vs_f64(case):
         Kn.conv2d_wgrad(dy, d(x), 3, 1, dw32, db32, d(sc), d(sh), accumulate=False)
         e32, e16 = _rel(dw32, dwref), _rel(dw, dwref)
         print("2xfp16 wgrad %s: f32 %.2e 2xfp16 %.2e" % (case, e32, e16))
+        yardstick_cap("2xfp16 wgrad %s" % (case,), e32, B * H * W)
         assert _ok(e16, e32, 2), (e16, e32)
         assert _rel(dbw, dy64.sum((0, 2, 3))) <= 1e-5
 
@@ -512,6 +523,7 @@ def test_conv1x1_split_load_vs_f64(case, npieces):
                                       stat_part=part)
     e32, esp = _rel(y_f32, yref), _rel(y, yref)
     print("sol fwd %s np=%d: f32 %.2e split-load %.2e" % (case, npc, e32, esp))
+    yardstick_cap("sol fwd %s np=%d" % (case, npc), e32, Cin)
     assert _ok(esp, e32, npc), (esp, e32)
     # without the partials epilogue: the same K order and chunking, so the same
     # bits — except with a residual, which that kernel adds in its transposed
@@ -545,6 +557,7 @@ def test_conv1x1_split_load_vs_f64(case, npieces):
         dx32 = Kn.conv2d_dgrad(d(dy), d(w32))
         e32, esp = _rel(dx32, dxref), _rel(dx, dxref)
         print("sol dgrad %s: f32 %.2e split-load %.2e" % (case, e32, esp))
+        yardstick_cap("sol dgrad %s" % (case,), e32, Cout)
         assert esp <= 2 * e32 + 1e-8, (esp, e32)
 
 
@@ -571,6 +584,7 @@ def test_conv1x1_split_load_16_channels(case, npieces):
     y = Kn.conv1x1_forward_split_load(d(x32), Kn.conv_weight_split(d(w32), 0, npieces), d(b32), ps, ph)
     e32, esp = _rel(y_f32, yref), _rel(y, yref)
     print("sol16 fwd %s np=%d: f32 %.2e split-load %.2e" % (case, npieces, e32, esp))
+    yardstick_cap("sol16 fwd %s np=%d" % (case, npieces), e32, Cin)
     assert _ok(esp, e32, npieces), (esp, e32)
     if npieces == 2:
         return
@@ -580,6 +594,7 @@ def test_conv1x1_split_load_16_channels(case, npieces):
     dx32 = Kn.conv2d_dgrad(d(dy), d(w32))
     e32, esp = _rel(dx32, dxref), _rel(dx, dxref)
     print("sol16 dgrad %s: f32 %.2e split-load %.2e" % (case, e32, esp))
+    yardstick_cap("sol16 dgrad %s" % (case,), e32, Cout)
     assert esp <= 2 * e32 + 1e-8, (esp, e32)
 
 
@@ -641,6 +656,7 @@ def test_wgrad1x1_split_load_vs_f64(case):
     Kn.conv2d_wgrad(d(dy), d(x), 1, 1, dw32, db32, ps, ph, accumulate=False)
     e32, esp = _rel(dw32, dwref), _rel(dw - 0.25, dwref)
     print("wgrad1 %s: f32 %.2e split-load %.2e" % (case, e32, esp))
+    yardstick_cap("wgrad1 %s" % (case,), e32, B * H * H)
     assert esp <= max(2 * e32 + 1e-8, 2.0 ** -21), (esp, e32)
     assert _rel(db + 0.5, dbref) <= 1e-5
 
@@ -696,6 +712,7 @@ def test_stem_s2d_vs_f64(B, H):
     y32 = Kn.conv2d_forward(d(x), d(w), d(b), 2)
     e32, esp = _rel(y32, yref), _rel(y, yref)
     print("stem s2d B=%d H=%d: f32 %.2e split %.2e" % (B, H, e32, esp))
+    yardstick_cap("stem s2d B=%d H=%d" % (B, H), e32, 147)
     # K = 147 keeps the exact-f32 chain below one f32 ulp (~4e-8 relative); the
     # split path rounds once per 16-term chunk (16 chunks): a few ulps is its level
     assert esp <= max(2 * e32, 4 * 2.0 ** -24), (esp, e32)
@@ -727,6 +744,8 @@ def test_stem_weight_gradient_s2d_vs_f64(B, H):
     e32, esp = _rel(dw32, wref), _rel(dw, wref)
     eb32, ebsp = _rel(db32, bref), _rel(db, bref)
     print("stem wgrad B=%d H=%d: f32 %.2e split %.2e | bias f32 %.2e split %.2e" % (B, H, e32, esp, eb32, ebsp))
+    yardstick_cap("stem wgrad B=%d H=%d" % (B, H), e32, min(B, 4) * (H // 2) ** 2)
+    yardstick_cap("stem dbias B=%d H=%d" % (B, H), eb32, min(B, 4) * (H // 2) ** 2)
     assert esp <= max(2 * e32, 4 * 2.0 ** -24), (esp, e32)
     assert ebsp <= max(2 * eb32, 4 * 2.0 ** -24), (ebsp, eb32)
     # accumulate=True adds onto what is there
@@ -816,6 +835,7 @@ def test_psa_halo_kernel_matches_per_tap_kernel_bit_for_bit(case, teams, npieces
     y_f32 = Kn.conv2d_forward(x32[sl].to(DEV), w32.to(DEV), b32.to(DEV), 1, res=res32[sl].to(DEV))
     e32, esp = _rel(y_f32, yref), _rel(outs["2"][0][sl], yref)
     print("halo %s np=%d: f32 %.2e split %.2e" % (case, npieces, e32, esp))
+    yardstick_cap("halo %s np=%d teams=%s" % (case, npieces, teams), e32, Cin * 9)
     assert _ok(esp, e32, npieces), (esp, e32)
 
 
