@@ -336,6 +336,33 @@ int ubpl_view_uncertainty_samples(const float* raw, int64_t sm, int64_t sv, int 
                                   float* int_dist, float* aug_coord, float* ext_dist, float* aext_dist,
                                   float* ext_views, float* mix_dist, float* unc, float* select, float* gate,
                                   void* stream);
+/* Cross-view pseudo-label targets: ubpl_decode_heatmaps_views' merge where every
+ * (target view, source view, sample) has its own matrix, and every view is a
+ * target — the training step's augmented views warped into one another's frames
+ * (the plumbing the reference ships and calls from a debug drawing only:
+ * warpmat per view, utils/augment.py:158-164; affine_back2, :36-47).
+ * View v, member m, sample n, joint k is the plane at hm + v*sv + m*sm + n*sb +
+ * k*H*W (strides in floats: the last stacks of [.., S, K, H, W] outputs are read
+ * in place).  mat [V][V][N][6] f32: mat[a][v][n] maps a 0-based cell of target
+ * view a to a 0-based cell of source view v, a pixel matrix in the convention
+ * above (kernels.train_pair_matrices).  Per element out[a][m][n][k][y][x], over
+ * the source views in ascending v:
+ *   v == a: with include_self != 0, s = p[y,x], c = 1 (the diagonal of mat is
+ *           never read); with include_self == 0 the view is skipped;
+ *   v != a: an exactly-identity matrix takes s = p[y,x], c = 1; otherwise (s, c)
+ *           = (s, cov) of the one sampling rule above under mat[a][v][n] (un-fused
+ *           f32, zero taps outside, a NaN or infinite position is outside).
+ *   The first contributing view sets num = s, den = c; later ones num = num + s,
+ *   den = den + c (sequential f32 sums); out = num / den (one IEEE f32 division)
+ *   where den > 0, else 0: ubpl_decode_heatmaps_views' rule, word for word.
+ * cover [V][N][H][W] (nullable) = den, written once, not per plane.
+ * 1 <= V <= 16, 1 <= M <= 8, include_self == 0 needs V >= 2, strides >= 0 and
+ * >= K*H*W wherever their count exceeds 1, out non-null (hipErrorInvalidValue
+ * otherwise).  out must not overlap hm.  No atomics, no cross-pixel sums:
+ * repeated launches give equal bits. */
+/*@ hm:f32[(V-1)*sv+(M-1)*sm+(N-1)*sb+(int64_t)K*H*W] mat:f32[(int64_t)V*V*N*6] out:f32[(int64_t)V*M*N*K*H*W] cover:f32[(int64_t)V*N*H*W] */
+int ubpl_merge_views_samples(const float* hm, int64_t sv, int64_t sm, int64_t sb, int V, int M, int N, int K,
+                             int H, int W, const float* mat, int include_self, float* out, float* cover, void* stream);
 /* EvaluationUtils.acc_pck (utils/evaluation.py:91-139).  errs/accs [K+1];
  * hits/valid [K] int32 (nullable) for cross-rank aggregation. */
 /*@ preds:f32[N*K*2] gts:f32[N*K*3] errs:f32[K+1] accs:f32[K+1] hits:i32[K] valid:i32[K] */

@@ -13,8 +13,11 @@ pseudo labels by the view-consistency rule of the training step (DESIGN.md §4);
 hands the views' matrices on as meta["viewmat"].  --pseudo-rule rate (with --sel-rate R, a share in
 (0, 1]) keeps the top share R of every batch's joints by softmax score (JointPseudoLoss2 in the
 step, DESIGN.md §4 "Rank-based pseudo-label selection") and logs each epoch's selection count
-("n_sel") and mean thresholds ("rate_thr1", "rate_thr2").  Every run logs the share of pseudo
-labels its rule selected per epoch ("sel_rate").
+("n_sel") and mean thresholds ("rate_thr1", "rate_thr2").  --pseudo-views merged / other takes the
+pseudo loss' targets of a view from both views' teacher maps warped into its frame (DESIGN.md §4,
+"Cross-view pseudo-label targets"; the matrices are handed on whenever it is not own); it combines
+with every rule.  Every run logs the share of pseudo labels its rule selected per epoch
+("sel_rate").
 
 Reads tests/golden/mouse_100_500_0.3/ (tools/pack_mouse.py).
 """
@@ -46,6 +49,7 @@ def parser():
     ap.add_argument("--pseudo-rule", default="score", choices=["score", "uncertainty", "score+uncertainty", "rate"])
     ap.add_argument("--dist-thr", type=float, default=None, help="distThrMax, source-image pixels")
     ap.add_argument("--sel-rate", type=float, default=None, help="pseudoSelRate of --pseudo-rule rate, in (0, 1]")
+    ap.add_argument("--pseudo-views", default="own", choices=["own", "merged", "other"])
     ap.add_argument("--pseudo-refine", default=None, choices=["none", "quarter", "taylor"])
     ap.add_argument("--pseudo-blur-sigma", type=float, default=None)
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "mouse_pck.json"))
@@ -93,6 +97,9 @@ def run(a, write=True, keep=None):
             args.pseudoRefine = a.pseudo_refine
         if a.pseudo_blur_sigma is not None:
             args.pseudoBlurSigma = a.pseudo_blur_sigma
+    with_mats = gated or a.pseudo_views != "own"
+    if a.pseudo_views != "own":
+        args.pseudoViews = a.pseudo_views
     models, emas, optims = [], [], []
     for _ in range(2):                                                 # :43-50 student, teacher per branch
         models.append(pose_model(a.model, data.kpsCount, "AvgPool"))
@@ -111,12 +118,12 @@ def run(a, write=True, keep=None):
             idx = list(idx)
             views, kps, mats = [], [], []
             for _ in range(2):                                         # DS_mds augCount = 2
-                x, k, *m = aug.views(idx, kps_all[idx], with_mats=gated)
+                x, k, *m = aug.views(idx, kps_all[idx], with_mats=with_mats)
                 views.append(x)
                 kps.append(k)
                 mats += m
             meta = {"kps": kps, "islabeled": [torch.tensor(isl_all[idx], device=dev)]}
-            if gated:
+            if with_mats:
                 meta["viewmat"] = mats
             yield views, None, meta
 
@@ -124,7 +131,8 @@ def run(a, write=True, keep=None):
                       "epochs": a.epochs, "augment": not a.no_aug, "seed": a.seed, "split": "Mouse_100_500_0.3",
                       "pck_ref": data.pck_ref, "pck_thr": data.pck_thr, "means": means,
                       "pseudo_rule": a.pseudo_rule, "dist_thr": a.dist_thr, "pseudo_refine": a.pseudo_refine,
-                      "pseudo_blur_sigma": a.pseudo_blur_sigma, "pseudo_sel_rate": a.sel_rate},
+                      "pseudo_blur_sigma": a.pseudo_blur_sigma, "pseudo_sel_rate": a.sel_rate,
+                      "pseudo_views": a.pseudo_views},
            "epochs": []}
     best = (-1.0, -1)
     t0 = time.time()

@@ -1,5 +1,6 @@
-"""What a pseudo-label rule of the training step costs on the headline step: the view-consistency
-rule (--rule uncertainty, the default) or the rank-based one (--rule rate).
+"""What a pseudo-label option of the training step costs on the headline step: the view-consistency
+rule (--rule uncertainty, the default), the rank-based one (--rule rate) or cross-view targets
+(--rule views).
 
 The bench's MT_UBPL step (2 students + 2 EMA teachers, HG2, 256x256, B=32, synthetic
 batches, captured in a HIP graph) with args.pseudoRule off ("score") and on
@@ -15,11 +16,14 @@ random similarity per (view, sample) as meta["viewmat"] (the rule's cost does no
 on what the matrices say).  --rule rate times args.pseudoRule = "rate" (--sel-rate) instead: per
 pseudo-loss call two ubpl_softmax_peak_scores reads (the student's stacks, the teachers' last
 stacks), two ubpl_rank_threshold launches and ubpl_loss_finalize_ranked in ubpl_loss_finalize's
-place.  One JSON line on stdout and in --out (default profiles/view_gate_step.json, for --rule
-rate profiles/rate_rule_step.json).  No GPU, no number.
+place.  --rule views times args.pseudoViews (--pseudo-views merged|other) under the score rule: one
+stack of the teachers' last stacks, the pair matrices and one ubpl_merge_views_samples launch in
+place of the per-view stacks of the teachers' full outputs.  One JSON line on stdout and in --out
+(default profiles/view_gate_step.json, for --rule rate profiles/rate_rule_step.json, for --rule
+views profiles/cross_view_step.json).  No GPU, no number.
 
-    python tools/view_gate_bench.py [--rule uncertainty|rate] [--steps 10] [--repeats 5] [--dist-thr 4]
-                                    [--sel-rate 0.5] [--out FILE]
+    python tools/view_gate_bench.py [--rule uncertainty|rate|views] [--steps 10] [--repeats 5] [--dist-thr 4]
+                                    [--sel-rate 0.5] [--pseudo-views merged] [--out FILE]
 """
 import argparse
 import json
@@ -50,13 +54,15 @@ def main():
     ap.add_argument("--steps", type=int, default=10, help="timed steps per variant per round")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--batch", type=int, default=32)
-    ap.add_argument("--rule", choices=("uncertainty", "rate"), default="uncertainty")
+    ap.add_argument("--rule", choices=("uncertainty", "rate", "views"), default="uncertainty")
     ap.add_argument("--dist-thr", type=float, default=4.0)
     ap.add_argument("--sel-rate", type=float, default=0.5)
+    ap.add_argument("--pseudo-views", choices=("merged", "other"), default="merged")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "rate_rule_step.json" if a.rule == "rate" else "view_gate_step.json")
+        a.out = os.path.join(ROOT, "profiles", {"rate": "rate_rule_step.json", "views": "cross_view_step.json"}.get(
+            a.rule, "view_gate_step.json"))
 
     import bench
     from ubpl_amd import _lib, kernels as Kn
@@ -88,6 +94,9 @@ def main():
     if a.rule == "rate":
         args_on.pseudoRule, args_on.pseudoSelRate = "rate", a.sel_rate
         rule_on = {"pseudoRule": "rate", "pseudoSelRate": a.sel_rate}
+    elif a.rule == "views":
+        args_on.pseudoViews = a.pseudo_views
+        rule_on = {"pseudoViews": a.pseudo_views}
     else:
         args_on.pseudoRule, args_on.distThrMax = "uncertainty", a.dist_thr
         rule_on = {"pseudoRule": "uncertainty", "distThrMax": a.dist_thr, "pseudoRefine": "taylor"}

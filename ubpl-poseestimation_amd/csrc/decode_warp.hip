@@ -8,9 +8,10 @@
 // (projects/MT_UBPL.py:186-205).  Here both directions are pixel-space 2x3 matrices, output
 // pixel -> source pixel, with the mirror folded in (kernels.view_matrices).
 //
-// One sampling rule for both kernels (include/ubpl_hip.h states it): un-fused f32 products and
-// sums, so the numpy restatement (tests/tta_ref.py) gives the same bits; zero taps outside; an
-// exactly-identity matrix takes the value itself.
+// One sampling rule for both kernels (include/ubpl_hip.h states it; warp_sample.h is its code,
+// shared with view_merge.hip): un-fused f32 products and sums, so the numpy restatement
+// (tests/tta_ref.py) gives the same bits; zero taps outside; an exactly-identity matrix takes the
+// value itself.
 //
 // decode: one 256-thread block per map (n, k).  A map is 16 KB, so the four bilinear taps of
 // every view are gathers that stay in the cache; what a map costs is the latency of V rounds of
@@ -20,66 +21,16 @@
 // and wave 0 finishes the map with the decode family's finish_map.  beats() is a total order
 // on (value, index), so the result does not depend on how the pixels are dealt to threads.
 #include "decode_common.h"
+#include "warp_sample.h"
 
 namespace {
 
-using ubpl::beats;
-using ubpl::finish_map;
+using namespace ubpl;   // beats, finish_map; Mat6, is_identity, sample and the *_rn helpers (warp_sample.h)
 
 constexpr int MAX_VIEWS = 16;
 
-// One rounding per product, sum and quotient (__fmul_rn / __fadd_rn / __fsub_rn / __fdiv_rn in
-// meaning).  The toolchain's own helpers of those names are plain operators compiled with
-// contraction allowed, and after inlining the compiler fuses their products and sums into FMAs,
-// which the numpy restatement cannot follow; contraction is off for everything in this file.
+// (the merge's sums and its quotient below are un-fused like the header's)
 #pragma clang fp contract(off)
-__device__ __forceinline__ float mul_rn(float a, float b) { return a * b; }
-__device__ __forceinline__ float add_rn(float a, float b) { return a + b; }
-__device__ __forceinline__ float sub_rn(float a, float b) { return a - b; }
-__device__ __forceinline__ float div_rn(float a, float b) { return a / b; }
-
-struct Mat6 {
-    float m[6];
-};
-
-__device__ __forceinline__ bool is_identity(const Mat6& a) {
-    return a.m[0] == 1.f && a.m[1] == 0.f && a.m[2] == 0.f && a.m[3] == 0.f && a.m[4] == 1.f && a.m[5] == 0.f;
-}
-
-__device__ __forceinline__ float tap(const float* __restrict__ p, int H, int W, int y, int x, float& c) {
-    const bool in = (unsigned)x < (unsigned)W && (unsigned)y < (unsigned)H;
-    c = in ? 1.f : 0.f;
-    return in ? p[y * W + x] : 0.f;
-}
-
-// a (1 - t) + b t, every product and sum its own rounding
-__device__ __forceinline__ float lerp_rn(float a, float b, float t, float u) {
-    return add_rn(mul_rn(a, u), mul_rn(b, t));
-}
-
-// The bilinear sample of plane p [H,W] at the source position of output pixel (x, y) under
-// matrix a, and the same formula over the in-bounds indicator (cov).  Outside — sx not in
-// (-1, W) or sy not in (-1, H), which a NaN or an infinity is not — both are 0; the test comes
-// before the float -> int conversion.
-__device__ __forceinline__ float sample(const float* __restrict__ p, int H, int W, const Mat6& a, int x, int y,
-                                        float& cov) {
-    const float fx = (float)x, fy = (float)y;
-    const float sx = add_rn(add_rn(mul_rn(a.m[0], fx), mul_rn(a.m[1], fy)), a.m[2]);
-    const float sy = add_rn(add_rn(mul_rn(a.m[3], fx), mul_rn(a.m[4], fy)), a.m[5]);
-    if (!(sx > -1.f && sx < (float)W && sy > -1.f && sy < (float)H)) {
-        cov = 0.f;
-        return 0.f;
-    }
-    const float x0f = floorf(sx), y0f = floorf(sy);
-    const float ax = sub_rn(sx, x0f), ay = sub_rn(sy, y0f);
-    const float bx = sub_rn(1.f, ax), by = sub_rn(1.f, ay);
-    const int x0 = (int)x0f, y0 = (int)y0f;
-    float c00, c01, c10, c11;
-    const float v00 = tap(p, H, W, y0, x0, c00), v01 = tap(p, H, W, y0, x0 + 1, c01);
-    const float v10 = tap(p, H, W, y0 + 1, x0, c10), v11 = tap(p, H, W, y0 + 1, x0 + 1, c11);
-    cov = lerp_rn(lerp_rn(c00, c01, ax, bx), lerp_rn(c10, c11, ax, bx), ay, by);
-    return lerp_rn(lerp_rn(v00, v01, ax, bx), lerp_rn(v10, v11, ax, bx), ay, by);
-}
 
 // out[v, plane, y, x] = sample of src[plane] under mat[v]; thread per output pixel.
 __global__ void __launch_bounds__(256) warp_views_kernel(const float* __restrict__ src, int64_t planes, int H, int W,
@@ -93,9 +44,7 @@ __global__ void __launch_bounds__(256) warp_views_kernel(const float* __restrict
         const int64_t pl = r / HW;
         const int px = (int)(r - pl * HW);
         const int y = px / W, x = px - y * W;
-        Mat6 a;
-#pragma unroll
-        for (int j = 0; j < 6; ++j) a.m[j] = mat[v * 6 + j];
+        const Mat6 a = load_mat6(mat + v * 6);
         const float* p = src + pl * HW;
         float cov;
         out[i] = is_identity(a) ? p[px] : sample(p, H, W, a, x, y, cov);
@@ -126,9 +75,7 @@ __global__ void __launch_bounds__(256) decode_views_kernel(const float* __restri
     for (int i = tid; i < HW; i += 256) {
         float num = 0.f, den = 0.f;
         for (int v = 0; v < V; ++v) {                  // (block-uniform: the matrices are scalar loads)
-            Mat6 a;
-#pragma unroll
-            for (int j = 0; j < 6; ++j) a.m[j] = mat[v * 6 + j];
+            const Mat6 a = load_mat6(mat + v * 6);
             const int kv = (swap != nullptr && swap[v] != 0) ? pk : k;
             const float* p = base + v * sv + (int64_t)kv * HW;
             float s, c;

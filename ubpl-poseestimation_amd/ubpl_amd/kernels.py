@@ -261,6 +261,9 @@ def _chk_maps(t, name, counts, strides, plane, signed=True):
         if len(counts) == 1:
             raise ValueError("ubpl_amd: %s holds %d floats, %d maps of stride %d need %d"
                              % (name, t.numel(), counts[0], strides[0], need))
+        if len(counts) > 2:
+            raise ValueError("ubpl_amd: %s holds %d floats, %s maps of strides %s need %d"
+                             % (name, t.numel(), " x ".join(map(str, counts)), ", ".join(map(str, strides)), need))
         raise ValueError("ubpl_amd: %s holds %d floats, %d x %d maps of strides %d, %d need %d"
                          % (name, t.numel(), *counts, *strides, need))
 
@@ -633,6 +636,84 @@ def train_back_matrices(viewmat, R, H):
     out = m * s                                                 # the linear part: a cell is R/H pixels
     out[..., 2::3] = m[..., 2::3]                               # C has no offset: the translation stays
     return out.to(F32).contiguous()
+
+
+# ---- cross-view pseudo-label targets (csrc/view_merge.hip)
+def train_pair_matrices(viewmat, R, H):
+    """The pair matrices of the training step's views for merge_views_samples.  viewmat, R, H as
+    train_back_matrices takes them (view v's matrix Mv: 0-based view input pixel -> 0-based
+    source-image pixel).  -> float32 [V,V,N,6] on viewmat's device: P[a][v][n] maps a 0-based
+    heatmap cell of view a to the 0-based heatmap cell of view v that shows the same source pixel,
+
+        P[a][v] = C^-1 o inv(Mv) o Ma o C,    C(c) = (R/H) c
+
+    — train_back_matrices' cell convention, so the gate and the targets agree.  In float64, in this
+    order: inv(Mv) by view_back_matrices' formula; L = inv(Mv) o Ma by compose_pixels' formula;
+    the linear part of P is L's, its translation L's divided by R/H; rounded once to float32.  The
+    diagonal a == v is written as exactly (1,0,0,0,1,0).  A singular Mv gives non-finite entries,
+    which the kernel's sampling rule counts as outside.  Tensor ops only: on the device it needs no
+    host synchronisation and can be captured."""
+    m = torch.stack(list(viewmat)) if isinstance(viewmat, (list, tuple)) else viewmat
+    if m.dim() != 3 or m.shape[-1] != 6:
+        raise ValueError("ubpl_amd: viewmat is [V,N,6], one pixel matrix per view and sample")
+    m = m.to(F64)
+    V = m.shape[0]
+    s = float(R) / float(H)
+    det = m[..., 0] * m[..., 4] - m[..., 1] * m[..., 3]
+    i0, i1, i3, i4 = m[..., 4] / det, -m[..., 1] / det, -m[..., 3] / det, m[..., 0] / det
+    i2 = -(i0 * m[..., 2] + i1 * m[..., 5])
+    i5 = -(i3 * m[..., 2] + i4 * m[..., 5])
+    inv = torch.stack([i0, i1, i2, i3, i4, i5], -1)         # [V,N,6]
+    a, b = inv.unsqueeze(0), m.unsqueeze(1)                  # a o b at [target a][source v]: inv(Mv) o Ma
+    rows = []
+    for r in (0, 3):
+        rows += [a[..., r] * b[..., 0] + a[..., r + 1] * b[..., 3],
+                 a[..., r] * b[..., 1] + a[..., r + 1] * b[..., 4],
+                 (a[..., r] * b[..., 2] + a[..., r + 1] * b[..., 5] + a[..., r + 2]) / s]
+    out = torch.stack(rows, -1).to(F32)                      # [V,V,N,6]
+    eye = (torch.arange(6, device=out.device) % 4 == 0).to(F32)   # (1,0,0,0,1,0) without a host -> device copy
+    diag = torch.eye(V, dtype=torch.bool, device=out.device).reshape(V, V, 1, 1)
+    return torch.where(diag, eye, out).contiguous()
+
+
+def merge_views_samples(hm, sv, sm, sb, V, M, N, K, H, W, mat, include_self=True, want_cover=False, out=None):
+    """Per-sample cross-view merge (ubpl_merge_views_samples): hm is a tensor whose first element
+    is view 0's, member 0's map (0, 0), with view, member and batch strides sv, sm, sb floats — a
+    [V,M,N,K,H,W] buffer, or the last stacks of [.., S, K, H, W] outputs through a view at an
+    element offset.  mat: device float32 [V,V,N,6] (train_pair_matrices).  include_self: a view's
+    own maps count in its target ("merged") or not ("other", V >= 2).  1 <= V <= 16, 1 <= M <= 8.
+    -> (out [V,M,N,K,H,W]: every view's maps as the mean of the views that cover each cell, warped
+        into its frame; cover [V,N,H,W] or None: the covering views' weight per cell);
+    out = (out, cover): write into these instead of allocating (cover None: not wanted)."""
+    if not 1 <= V <= MAX_VIEWS:
+        raise ValueError("ubpl_amd: merge_views_samples takes 1 to %d views, got %d" % (MAX_VIEWS, V))
+    if not 1 <= M <= 8:
+        raise ValueError("ubpl_amd: merge_views_samples takes 1 to 8 members, got %d" % M)
+    if not include_self and V < 2:
+        raise ValueError("ubpl_amd: merge_views_samples without a view's own maps needs at least 2 views")
+    plane = K * H * W
+    _chk_maps(hm, "hm", (V, M, N), (sv, sm, sb), plane, signed=False)
+    if hm is None or any(n > 1 and st < plane for n, st in ((V, sv), (M, sm), (N, sb))):
+        raise ValueError("ubpl_amd: hm's strides %d, %d, %d are at least one block of %d floats"
+                         % (sv, sm, sb, plane))
+    _chk(mat, "mat")
+    if mat is None or mat.numel() != V * V * N * 6:
+        raise ValueError("ubpl_amd: mat is [V,V,N,6], one pixel matrix per view pair and sample")
+    res, cover = _outs(out, hm.device, ((V, M, N, K, H, W), True), ((V, N, H, W), want_cover))
+    _chk(res, "out")
+    _chk(cover, "cover")
+    if res is None or res.numel() != V * M * N * plane:
+        raise ValueError("ubpl_amd: out holds %d floats, [V,M,N,K,H,W] needs %d"
+                         % (0 if res is None else res.numel(), V * M * N * plane))
+    if cover is not None and cover.numel() != V * N * H * W:
+        raise ValueError("ubpl_amd: cover holds %d floats, [V,N,H,W] needs %d" % (cover.numel(), V * N * H * W))
+    lo, hi = hm.data_ptr(), hm.data_ptr() + ((V - 1) * sv + (M - 1) * sm + (N - 1) * sb + plane) * 4
+    for t in (res, cover):
+        if t is not None and t.numel() and t.data_ptr() < hi and lo < t.data_ptr() + t.numel() * 4:
+            raise ValueError("ubpl_amd: merge_views_samples writes tensors that do not overlap its input")
+    call("ubpl_merge_views_samples", hm, int(sv), int(sm), int(sb), V, M, N, K, H, W, mat, int(bool(include_self)),
+         res, cover)
+    return res, cover
 
 
 def fliplr(x, out=None):

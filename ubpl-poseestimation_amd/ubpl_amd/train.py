@@ -141,12 +141,14 @@ def _pseudo_rate(n_sel, n_ps, guarded=False):
     return int(n_sel) / int(n_ps)
 
 
-def _pseudo_line(bat, kind, args, rate, n_sel, n_ps, scores, dist_thr=None, sel_rate=None, rate_thr=()):
+def _pseudo_line(bat, kind, args, rate, n_sel, n_ps, scores, dist_thr=None, sel_rate=None, rate_thr=(), views=None):
     """dist_thr: the view-consistency rule's threshold, shown only when that rule is on.
     sel_rate, rate_thr: the "rate" rule's share and the step's thresholds (per model rateThr1,
-    rateThr2), shown only when that rule is on."""
+    rateThr2), shown only when that rule is on.  views: "merged" / "other", shown only with
+    cross-view targets."""
     thr = format(args.pseudoScoreThr, ".2f") + ("" if dist_thr is None else " distThr:" + format(dist_thr, ".2f"))
     thr += "" if sel_rate is None else " selRate:" + format(sel_rate, ".2f")
+    thr += "" if views is None else " views:" + views
     tail = "" if sel_rate is None else ", rateThr: [{}]".format(", ".join(format(v, ".4f") for v in rate_thr))
     print("batch.{}{} (scoreThr:{}): {} ({}/{}), pseudo-score: [{}]{}".format(
         format(bat + 1, "5d"), kind, thr, format(rate, ".2f"),
@@ -172,7 +174,8 @@ def _mt_ubpl_core(models, models_ema, optims, args, augs_imgMap, augs_heatmaps, 
     rule = VG.options(args)                              # the view-consistency rule (off: the score rule)
     gated = rule.on and use_ep
     ranked = rule.sel_rate is not None and use_ep        # the "rate" rule: JointPseudoLoss2 for JointPseudoLoss3
-    if gated:
+    cross = rule.cross and use_ep                        # pseudoViews "merged" / "other": cross-view targets
+    if gated or cross:
         VG.check_batch(rule, meta, A, M)                     # ValueError before any launch
     for o in optims:
         o.zero_grad()
@@ -213,7 +216,17 @@ def _mt_ubpl_core(models, models_ema, optims, args, augs_imgMap, augs_heatmaps, 
     K = outs[0][0].shape[2]
     zero = torch.zeros((), device=dev)
     zcnt = torch.zeros(4, dtype=torch.int32, device=dev)
-    if gated:
+    if cross:
+        # the teachers' last stacks of every view in one buffer, on the main stream after the join:
+        # merged across the views into every view's targets (one launch), and decoded for the gate
+        with torch.no_grad():
+            last = torch.stack([torch.stack([outs_ema[j][a][:, -1] for j in range(M)]) for a in range(A)])
+            xt = VG.cross_view_targets(rule, last, meta["viewmat"], imgs[0].shape[-1])
+            tgs = [xt[a].unsqueeze(2) for a in range(A)]     # [M,B,1,K,H,W]: the pseudo losses' St = 1
+            if gated:                                        # (the gate is each view's own maps' business)
+                gate = VG.view_gate(rule, [last[a].unsqueeze(2) for a in range(A)], meta["viewmat"],
+                                    imgs[0].shape[-1])
+    elif gated:
         # the teachers' stacked outputs per view, built once: decoded for the gate here, on the
         # main stream after the join, and shared by the students' pseudo losses below
         with torch.no_grad():
@@ -231,12 +244,12 @@ def _mt_ubpl_core(models, models_ema, optims, args, augs_imgMap, augs_heatmaps, 
                 s_e, c_e, sc_e = _pseudo_gated(outs[mi][a], tgs[a], nega, S, rule.thr, gate)
                 ps_scores.append(sc_e)
             elif ranked:
-                tg = torch.stack([outs_ema[j][a] for j in range(M)])
+                tg = tgs[a] if cross else torch.stack([outs_ema[j][a] for j in range(M)])
                 s_e, c_e, sc_e, thr = _pseudo_ranked(outs[mi][a], tg, nega, S, rank)
                 ps_scores.append(sc_e)
                 thr_m.append(thr)                            # rateThr1 [S], rateThr2 [S]
             elif use_ep:
-                tg = torch.stack([outs_ema[j][a] for j in range(M)])
+                tg = tgs[a] if cross else torch.stack([outs_ema[j][a] for j in range(M)])
                 s_e, c_e, sc_e = _pseudo(outs[mi][a], tg, nega, S, args.pseudoScoreThr)
                 ps_scores.append(sc_e)
             else:
@@ -308,7 +321,8 @@ def _mt_ubpl_records(host, bat, L, mtc_n, B, use_ep, counters, args, verbose, gu
         if verbose:
             rule = VG.options(args)
             _pseudo_line(bat, "", args, rate, n_sel, n_ps, host[L.scores()], rule.dist_thr if rule.on else None,
-                         rule.sel_rate if L.rate_thr else None, host[L.rate_thr] if L.rate_thr else ())
+                         rule.sel_rate if L.rate_thr else None, host[L.rate_thr] if L.rate_thr else (),
+                         rule.views if rule.cross else None)
 
 
 def train_mt_ubpl(trainLoader, models, models_ema, optims, args, verbose=True, pseudo_counts=None):
@@ -322,7 +336,11 @@ def train_mt_ubpl(trainLoader, models, models_ema, optims, args, verbose=True, p
     JointPseudoLoss3's place ("Rank-based pseudo-label selection").  pseudo_counts: a
     dict that receives the epoch's totals of the steps' pseudo-label counts, "n_pseudo" and "n_sel"
     (what the active rule selected), and under the "rate" rule "steps" and the sums over the steps of
-    the models' mean thresholds, "rate_thr1" and "rate_thr2"."""
+    the models' mean thresholds, "rate_thr1" and "rate_thr2".
+    args.pseudoViews "merged" / "other" (default "own") takes the pseudo loss' targets of a view from
+    every view's teacher maps warped into its frame, with or without its own (DESIGN.md §4,
+    "Cross-view pseudo-label targets"); the batches then carry meta["viewmat"].  It combines with
+    every pseudoRule."""
     rule = VG.options(args)
     if rule.on:
         VG.constants(rule, models[0].flat_params.device)     # host -> device, ahead of any capture

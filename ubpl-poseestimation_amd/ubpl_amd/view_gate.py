@@ -10,13 +10,20 @@ teacher's peaks agree across the views and with the other teachers within args.d
 The gate then masks the ensemble-pseudo loss (step_losses._pseudo_gated).
 
 RULES is the one list of the step's pseudo-label rules, so the "rate" rule (rank-based selection,
-step_losses._pseudo_ranked) has its option check here too; it needs no gate and no constants."""
+step_losses._pseudo_ranked) has its option check here too; it needs no gate and no constants.
+
+VIEWS is the list of args.pseudoViews, where the pseudo loss of view a takes its targets from
+("Cross-view pseudo-label targets"): "own" — the teachers' maps of view a, the step
+as the reference has it; "merged" — the mean of every view's maps warped into view a's frame;
+"other" — the same without view a's own.  It combines with every rule: the rule says which joints
+are kept, the views what they are pulled towards."""
 import torch
 
 from . import kernels as Kn
 from . import predict_args as PA
 
 RULES = ("score", "uncertainty", "score+uncertainty", "rate")
+VIEWS = ("own", "merged", "other")
 
 
 def check_sel_rate(rule, value):
@@ -31,13 +38,18 @@ def check_sel_rate(rule, value):
 
 class GateOptions:
     """The rule's options read from a step's args, checked on the host: every existing namespace
-    (none of the four attributes) is the score rule, `on` False.  `on` is the view-consistency
-    gate; the "rate" rule (sel_rate not None) selects by rank instead and is not combined with it."""
+    (none of the attributes) is the score rule on each view's own targets, `on` and `cross` False.
+    `on` is the view-consistency gate; the "rate" rule (sel_rate not None) selects by rank instead
+    and is not combined with it; `cross` is cross-view targets (views "merged" or "other")."""
 
     def __init__(self, args):
         self.rule = getattr(args, "pseudoRule", "score")
         if self.rule not in RULES:
             raise ValueError("ubpl_amd: pseudoRule is one of %s, got %r" % (", ".join(RULES), self.rule))
+        self.views = getattr(args, "pseudoViews", "own")
+        if self.views not in VIEWS:
+            raise ValueError("ubpl_amd: pseudoViews is one of %s, got %r" % (", ".join(VIEWS), self.views))
+        self.cross = self.views != "own"
         self.sel_rate = None                                 # the "rate" rule's share of joints kept
         if self.rule == "rate":
             self.sel_rate = check_sel_rate(self.rule, getattr(args, "pseudoSelRate", None))
@@ -67,7 +79,8 @@ def options(args):
     keeps them alive.  An entry is a few floats, one per option set a process ever trains with."""
     key = (getattr(args, "pseudoRule", "score"), getattr(args, "distThrMax", None),
            getattr(args, "pseudoRefine", None), getattr(args, "pseudoBlurSigma", None),
-           getattr(args, "pseudoScoreThr", None), getattr(args, "pseudoSelRate", None))
+           getattr(args, "pseudoScoreThr", None), getattr(args, "pseudoSelRate", None),
+           getattr(args, "pseudoViews", "own"))
     try:
         opts = _OPTIONS.get(key)
     except TypeError:                                        # an unhashable value: let the checks name it
@@ -78,27 +91,32 @@ def options(args):
 
 
 def refuse(args, where):
-    """The steps the rule is not wired into say so instead of ignoring the option."""
+    """The steps the rule and the cross-view targets are not wired into say so instead of ignoring
+    the option."""
     opts = options(args)
+    if opts.cross:
+        raise ValueError("ubpl_amd: pseudoViews %r is built into train_mt_ubpl only, not %s" % (opts.views, where))
     if opts.on or opts.sel_rate is not None:
         raise ValueError("ubpl_amd: pseudoRule %r is built into train_mt_ubpl only, not %s"
                          % (args.pseudoRule, where))
 
 
 def check_batch(opts, meta, A, M):
-    """The rule against a batch, before any launch: it needs the views' matrices and two views."""
-    if not opts.on:
-        return
-    if A < 2:
-        raise ValueError("ubpl_amd: pseudoRule %r compares a sample's augmented views: at least 2, got %d"
-                         % (opts.rule, A))
-    if A > Kn.MAX_VIEWS or not 1 <= M <= 8:
-        raise ValueError("ubpl_amd: pseudoRule %r takes at most %d views and 8 teachers, got %d and %d"
-                         % (opts.rule, Kn.MAX_VIEWS, A, M))
-    vm = meta.get("viewmat") if isinstance(meta, dict) else None
-    if vm is None or len(vm) != A:
-        raise ValueError('ubpl_amd: pseudoRule %r needs meta["viewmat"]: one [B,6] float32 matrix table per view '
-                         "(DeviceAugment.views(with_mats=True))" % opts.rule)
+    """The rule and the cross-view targets against a batch, before any launch: each needs the views'
+    matrices and two views."""
+    for on, what, does in ((opts.on, "pseudoRule %r" % opts.rule, "compares"),
+                           (opts.cross, "pseudoViews %r" % opts.views, "merges")):
+        if not on:
+            continue
+        if A < 2:
+            raise ValueError("ubpl_amd: %s %s a sample's augmented views: at least 2, got %d" % (what, does, A))
+        if A > Kn.MAX_VIEWS or not 1 <= M <= 8:
+            raise ValueError("ubpl_amd: %s takes at most %d views and 8 teachers, got %d and %d"
+                             % (what, Kn.MAX_VIEWS, A, M))
+        vm = meta.get("viewmat") if isinstance(meta, dict) else None
+        if vm is None or len(vm) != A:
+            raise ValueError('ubpl_amd: %s needs meta["viewmat"]: one [B,6] float32 matrix table per view '
+                             "(DeviceAugment.views(with_mats=True))" % what)
 
 
 def constants(opts, dev):
@@ -141,3 +159,19 @@ def view_gate(opts, tgs, viewmat, R):
     Kn.view_uncertainty_samples(sub.view(-1), B * K * 2, M * B * K * 2, M, A, B, K, back, dist_thr,
                                 out=(None,) * 9 + (select, gate))
     return gate
+
+
+def cross_view_targets(opts, last, viewmat, R):
+    """The pseudo loss' targets of every view under args.pseudoViews "merged" / "other".  last: the
+    teachers' last stacks of every view, [A,M,B,K,H,W] contiguous; viewmat: per view a device float32
+    [B,6]; R: the views' input side.  -> xt [A,M,B,K,H,W]: xt[a] is every teacher's maps of all views
+    (without view a's own under "other") warped into view a's frame and averaged over the views that
+    cover each cell.  One ubpl_merge_views_samples launch; the pair matrices are a handful of
+    elementwise tensor ops.  No host synchronisation."""
+    A, M, B, K, H, W = last.shape
+    dev = last.device
+    pair = Kn.train_pair_matrices([v.to(dev, non_blocking=True).float().reshape(B, 6) for v in viewmat], R, H)
+    blk = K * H * W
+    xt, _ = Kn.merge_views_samples(last.view(-1), M * B * blk, B * blk, blk, A, M, B, K, H, W, pair,
+                                   include_self=opts.views == "merged")
+    return xt
