@@ -627,3 +627,125 @@ def test_zero_pseudo_count_raises_like_the_reference():
         with pytest.raises(ZeroDivisionError):
             dual(0, verbose)
         dual(7, verbose)
+
+
+KERNELS_DIR = os.path.join(ROOT, "ubpl-poseestimation_amd", "ubpl_amd", "kernels")
+
+
+def _kernel_sources():
+    return {f[:-3]: open(os.path.join(KERNELS_DIR, f)).read() for f in sorted(os.listdir(KERNELS_DIR))
+            if f.endswith(".py")}
+
+
+def _entries_named(source):
+    """The C entries a wrapper source names: the first string argument of _lib.call / call /
+    _workspace / _slab, and the attributes read off _lib.lib()."""
+    import ast
+    found = set()
+    for node in ast.walk(ast.parse(source)):
+        if isinstance(node, ast.Call) and node.args and isinstance(node.args[0], ast.Constant) \
+                and isinstance(node.args[0].value, str):
+            f = node.func
+            if (isinstance(f, ast.Name) and f.id in ("call", "_workspace", "_slab")) or \
+                    (isinstance(f, ast.Attribute) and f.attr == "call"):
+                found.add(node.args[0].value)
+        if isinstance(node, ast.Attribute) and isinstance(node.value, ast.Call) \
+                and isinstance(node.value.func, ast.Attribute) and node.value.func.attr == "lib":
+            found.add(node.attr)
+    return found
+
+
+def test_every_entry_the_wrappers_name_is_declared():
+    """A misspelt entry name in a launch or a size query fails here, not first on a GPU."""
+    from ubpl_amd import _lib
+    named = set().union(*(_entries_named(src) for src in _kernel_sources().values()))
+    declared = set(_lib.signatures())
+    assert named <= declared, sorted(named - declared)
+    assert all(n.startswith("ubpl_") for n in named)
+    assert len(named) >= 84          # what the same walk found in the one-file kernels.py this package replaced
+
+
+# per family module: a wrapper that asks the library for no size, its arguments on CPU tensors, its entry
+def _seam_cases():
+    x = torch.zeros(2, 4, 8, 8)                       # the smallest plane pool_fuse_ok takes with W/4 a power of two
+    M, V, N, K = 2, 2, 1, 2
+    bn = tuple(torch.zeros(4) for _ in range(8))
+    pts, thr = torch.zeros(M * V * N * K * 2), torch.zeros(1)
+    return {
+        "render_loss": ("render_heatmaps", (torch.zeros(2, 2, 3), (8, 8), 8, 8), "ubpl_render_heatmaps"),
+        "decode": ("fliplr", (x,), "ubpl_fliplr"),
+        "views": ("view_uncertainty", (pts, V * N * K * 2, M, V, N, K, torch.zeros(V, 6), thr),
+                  "ubpl_view_uncertainty"),
+        "optim": ("scale_", (x, 2.0), "ubpl_scale_"),
+        "bn": ("bn_forward_stats_maxpool", (x, None, bn, 1e-5, 0.1, torch.zeros(8, dtype=torch.float64)),
+               "ubpl_bn_forward_stats_maxpool"),
+        "conv": ("conv_weight_flip", (torch.zeros(4, 4, 3, 3),), "ubpl_conv_weight_flip"),
+        "pool": ("maxpool2x2", (x,), "ubpl_maxpool2x2_forward"),
+        "augment": ("image_mean_u8", (torch.zeros(2, 8, 8, 3, dtype=torch.uint8),), "ubpl_image_mean_u8"),
+    }
+
+
+def test_every_family_module_launches_through_the_one_seam(monkeypatch):
+    """_lib.call, replaced once, sees the launch of a wrapper of every family module, and
+    _check._chk, replaced once, is the tensor check of all of them (the tensors here are on the CPU)."""
+    import importlib
+    from ubpl_amd import _lib, kernels as Kn
+    from ubpl_amd.kernels import _check
+    cases = _seam_cases()
+    launching = {m for m, src in _kernel_sources().items() if re.search(r"^\s+_lib\.call\(", src, re.M)}
+    assert launching == set(cases), launching ^ set(cases)
+    seen = []
+    monkeypatch.setattr(_lib, "call", lambda name, *a: seen.append((name, a)))
+    monkeypatch.setattr(_check, "_chk", lambda t, name, dtype=None: None)
+    for mod, (fn, args, entry) in cases.items():
+        wrapper = getattr(importlib.import_module("ubpl_amd.kernels." + mod), fn)
+        assert wrapper is getattr(Kn, fn) and wrapper.__module__ == "ubpl_amd.kernels." + mod
+        del seen[:]
+        wrapper(*args)
+        assert [name for name, _ in seen] == [entry], (mod, seen)
+    # the two uncertainty wrappers through their shared checks: ten outputs, and eleven with the gate
+    M, V, N, K = 2, 2, 1, 2
+    raw, thr = torch.zeros(V * M * N * K * 2), torch.zeros(1)
+    outs = Kn.view_uncertainty(raw, V * N * K * 2, M, V, N, K, torch.zeros(V, 6), thr)
+    assert len(outs) == len(Kn.UNC_OUTPUTS) == 10 and outs[0].shape == (M, V, N, K, 2) and outs[-1].shape == (M, N, K)
+    outs = Kn.view_uncertainty_samples(raw, N * K * 2, M * N * K * 2, M, V, N, K, torch.zeros(V, N, 6), thr)
+    assert len(outs) == 11 and outs[-2].shape == (M, N, K) and outs[-1].shape == (N, K)
+    assert seen[-1][0] == "ubpl_view_uncertainty_samples" and seen[-1][1][-11:] == outs
+    with pytest.raises(ValueError, match="1 to 8 members"):
+        Kn.view_uncertainty_samples(raw, N * K * 2, M * N * K * 2, 9, V, N, K, torch.zeros(V, N, 6), thr)
+    with pytest.raises(ValueError, match="2 to 16 views"):
+        Kn.view_uncertainty(raw, V * N * K * 2, M, 1, N, K, torch.zeros(V, 6), thr)
+    with pytest.raises(ValueError, match="back is \\[V,N,6\\]"):
+        Kn.view_uncertainty_samples(raw, N * K * 2, M * N * K * 2, M, V, N, K, torch.zeros(1, 6), thr)
+    assert Kn.call is not _lib.call                   # the alias keeps what it was bound to: no wrapper reads it
+
+
+def test_view_geometry_needs_no_library(monkeypatch):
+    """view_geometry is pure torch: it has no relative import, and its source runs, giving the
+    package's results, while ubpl_amd._lib cannot be used."""
+    import ast
+    import importlib.util
+    import sys
+    import types
+    import ubpl_amd
+    from ubpl_amd import kernels as Kn
+    path = os.path.join(KERNELS_DIR, "view_geometry.py")
+    imports = [n for n in ast.walk(ast.parse(open(path).read())) if isinstance(n, (ast.Import, ast.ImportFrom))]
+    assert all(isinstance(n, ast.Import) for n in imports), "view_geometry imports from the package"
+    assert {a.name for n in imports for a in n.names} == {"math", "torch"}
+
+    class Unusable(types.ModuleType):
+        def __getattr__(self, name):
+            raise ImportError("ubpl_amd._lib is not importable here (%s)" % name)
+    stub = Unusable("ubpl_amd._lib")
+    monkeypatch.setitem(sys.modules, "ubpl_amd._lib", stub)
+    monkeypatch.setattr(ubpl_amd, "_lib", stub)
+    spec = importlib.util.spec_from_file_location("ubpl_amd.kernels.view_geometry", path)
+    VG = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(VG)                       # (not entered into sys.modules)
+    img, hm, swap = VG.view_matrices([(0, 1), (30, 1.25)], True, 64, 16)
+    for a, b in zip((img, hm, swap), Kn.view_matrices([(0, 1), (30, 1.25)], True, 64, 16)):
+        assert torch.equal(a, b)
+    assert torch.equal(VG.view_back_matrices(hm), Kn.view_back_matrices(hm))
+    vm = img.reshape(4, 1, 6)
+    assert torch.equal(VG.train_pair_matrices(vm, 64, 16), Kn.train_pair_matrices(vm, 64, 16))

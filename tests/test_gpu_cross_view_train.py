@@ -260,12 +260,12 @@ def test_captured_step_matches_eager(monkeypatch):
 
 
 def _calls_of(monkeypatch, **opts):
-    """One eager step of batch 0 -> (Counter of Kn.call names, records, state)."""
-    from ubpl_amd import kernels as Kn
+    """One eager step of batch 0 -> (Counter of _lib.call names, records, state)."""
+    from ubpl_amd import _lib
     calls = []
-    real = Kn.call
+    real = _lib.call
     with monkeypatch.context() as mp:
-        mp.setattr(Kn, "call", lambda name, *a: (calls.append(name), real(name, *a))[1])
+        mp.setattr(_lib, "call", lambda name, *a: (calls.append(name), real(name, *a))[1])
         setup = _setup(**opts)
         host, L = _one_step(*setup, _batches()[0])
     return collections.Counter(calls), host, _state(*setup[:3]), L
@@ -342,11 +342,11 @@ def test_pseudo_losses_read_a_last_stack_alone_as_they_read_it_in_place():
 
 
 def test_errors_before_any_launch(eager, monkeypatch):
-    from ubpl_amd import kernels as Kn
+    from ubpl_amd import _lib
     from ubpl_amd import train as T
     calls = []
-    real = Kn.call
-    monkeypatch.setattr(Kn, "call", lambda name, *a: (calls.append(name), real(name, *a))[1])
+    real = _lib.call
+    monkeypatch.setattr(_lib, "call", lambda name, *a: (calls.append(name), real(name, *a))[1])
     views, _, meta = _batches()[0]
     with pytest.raises(ValueError, match="pseudoViews is one of own, merged, other"):
         _train([(views, None, meta)], *_setup(pseudoViews="all"))

@@ -232,18 +232,18 @@ def test_bn_backward_pool_vs_three_launches(shape):
 
 
 def _model_run(fuse, monkeypatch, imgs, dpreds):
-    from ubpl_amd import hourglass as HG, hourglass_exec
+    from ubpl_amd import _lib, hourglass as HG, hourglass_exec
     monkeypatch.setattr(hourglass_exec, "_POOL_FUSE", fuse)      # (the executor's module reads the flag)
     torch.manual_seed(0)
     model = HG.StackedHourglass(16, 2, "default")
     model.train()
     # the library calls of one forward + backward, counted at the wrappers' one way in
-    real, log = HG.Kn.call, []
-    monkeypatch.setattr(HG.Kn, "call", lambda name, *a: (log.append(name), real(name, *a))[1])
+    real, log = _lib.call, []
+    monkeypatch.setattr(_lib, "call", lambda name, *a: (log.append(name), real(name, *a))[1])
     preds = model(imgs.to(DEV))
     preds.backward(dpreds.to(DEV))
     torch.cuda.synchronize()
-    monkeypatch.setattr(HG.Kn, "call", real)
+    monkeypatch.setattr(_lib, "call", real)
     grads = {n: p.grad.detach().double().cpu() for n, p in model.named_parameters() if p.grad is not None}
     return preds.detach().double().cpu(), grads, log
 

@@ -151,16 +151,16 @@ def test_flip_test_of_a_symmetric_image_is_mirror_consistent(prec):
 
 @pytest.mark.parametrize("prec", PRECISIONS)
 def test_frozen_means_frozen(prec, monkeypatch):
-    from ubpl_amd import Predictor, kernels as Kn
+    from ubpl_amd import Predictor, _lib
     models = [_model(9, 1, prec), _model(9, 1, prec, seed=1)]
     P = Predictor(models, flip_test=True, graph=False)
     counts = {}
-    real = Kn.call
+    real = _lib.call
 
     def counting(name, *a):
         counts[name] = counts.get(name, 0) + 1
         return real(name, *a)
-    monkeypatch.setattr(Kn, "call", counting)
+    monkeypatch.setattr(_lib, "call", counting)
     x = _imgs(2, 128, torch.Generator().manual_seed(13))
     P.predict(x, *_cs(2, 128))
     assert counts.get("ubpl_decode_heatmaps_flip") == 2 and counts.get("ubpl_fliplr") == 1

@@ -192,10 +192,10 @@ def test_captured_step_matches_eager(monkeypatch):
 
 
 def test_record_without_the_rule_is_unchanged(eager, monkeypatch):
-    from ubpl_amd import kernels as Kn
+    from ubpl_amd import _lib
     calls = []
-    real = Kn.call
-    monkeypatch.setattr(Kn, "call", lambda name, *a: (calls.append(name), real(name, *a))[1])
+    real = _lib.call
+    monkeypatch.setattr(_lib, "call", lambda name, *a: (calls.append(name), real(name, *a))[1])
     plain, L = _one_step(*_setup())                                     # a namespace without the new attributes
     new = ("ubpl_softmax_peak_scores", "ubpl_rank_threshold", "ubpl_loss_finalize_ranked", "ubpl_loss_finalize_rank")
     assert not any(n in new for n in calls)
@@ -221,11 +221,11 @@ def test_record_without_the_rule_is_unchanged(eager, monkeypatch):
 
 
 def test_refusals_before_any_launch(eager, monkeypatch):
-    from ubpl_amd import kernels as Kn
+    from ubpl_amd import _lib
     from ubpl_amd import train as T
     calls = []
-    real = Kn.call
-    monkeypatch.setattr(Kn, "call", lambda name, *a: (calls.append(name), real(name, *a))[1])
+    real = _lib.call
+    monkeypatch.setattr(_lib, "call", lambda name, *a: (calls.append(name), real(name, *a))[1])
     models, emas, optims, args = _setup(pseudoRule="rate", pseudoSelRate=SEL_RATE)
     imgs, hms, meta = _batch()
     with pytest.raises(ValueError, match="train_mt_ubpl only"):

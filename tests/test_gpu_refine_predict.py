@@ -78,7 +78,7 @@ def _by_hand(hm, raw, refine, sigma, center, scale):
 
 
 def test_refine_none_is_the_predictor_of_before(monkeypatch):
-    from ubpl_amd import Predictor, kernels as Kn
+    from ubpl_amd import Predictor, _lib
     x = _imgs(3, torch.Generator().manual_seed(31))
     center, scale = _cs(3)
     old = Predictor(_models(), flip_test=True, flip_pairs=PAIRS)
@@ -91,8 +91,8 @@ def test_refine_none_is_the_predictor_of_before(monkeypatch):
             assert _eq(a[key], b[key]), key
     # and nothing new is launched
     names = []
-    real = Kn.call
-    monkeypatch.setattr(Kn, "call", lambda name, *a: (names.append(name), real(name, *a))[1])
+    real = _lib.call
+    monkeypatch.setattr(_lib, "call", lambda name, *a: (names.append(name), real(name, *a))[1])
     Predictor(_models(), refine="none", graph=False).pseudo_label(x, center, scale)
     assert "ubpl_refine_peaks" not in names and names.count("ubpl_decode_heatmaps_flip") == 2
     names.clear()

@@ -86,7 +86,7 @@ CALLS = (lambda P, x, c, s: P.predict(x, c, s, return_heatmaps=True), lambda P, 
 
 @pytest.mark.parametrize("flip", [False, True])
 def test_tta_none_and_the_identity_view_are_the_predictor_of_before(flip, monkeypatch):
-    from ubpl_amd import Predictor, kernels as Kn
+    from ubpl_amd import Predictor, _lib
     x = _imgs(3, torch.Generator().manual_seed(41))
     center, scale = _cs(3)
     kw = dict(flip_test=flip, flip_pairs=PAIRS if flip else None, refine="taylor")
@@ -101,8 +101,8 @@ def test_tta_none_and_the_identity_view_are_the_predictor_of_before(flip, monkey
         P.release()
     # tta=None launches what it launched; the views launch their two kernels instead
     names = []
-    real = Kn.call
-    monkeypatch.setattr(Kn, "call", lambda name, *a: (names.append(name), real(name, *a))[1])
+    real = _lib.call
+    monkeypatch.setattr(_lib, "call", lambda name, *a: (names.append(name), real(name, *a))[1])
     Predictor(_models(), tta=None, graph=False, flip_test=flip).predict(x)
     assert names.count("ubpl_decode_heatmaps_flip") == 2 and names.count("ubpl_fliplr") == int(flip)
     assert "ubpl_warp_views" not in names and "ubpl_decode_heatmaps_views" not in names

@@ -191,7 +191,7 @@ def test_chunks_concatenate_on_the_right_axes():
 
 
 def test_uncertainty_off_is_the_predictor_of_before(monkeypatch):
-    from ubpl_amd import Predictor, kernels as Kn
+    from ubpl_amd import Predictor, _lib
     x = _imgs(2, torch.Generator().manual_seed(64))
     center, scale = _cs(2)
     kw = dict(tta=VIEWS3, flip_test=True, flip_pairs=PAIRS, refine="taylor")
@@ -209,8 +209,8 @@ def test_uncertainty_off_is_the_predictor_of_before(monkeypatch):
     for P in (old, off, on):
         P.release()
     names = []
-    real = Kn.call
-    monkeypatch.setattr(Kn, "call", lambda name, *a: (names.append(name), real(name, *a))[1])
+    real = _lib.call
+    monkeypatch.setattr(_lib, "call", lambda name, *a: (names.append(name), real(name, *a))[1])
     Predictor(_models(), graph=False, **kw).predict(x)
     before = list(names)
     names.clear()

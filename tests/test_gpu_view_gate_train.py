@@ -270,10 +270,10 @@ def test_captured_step_matches_eager(monkeypatch):
 
 
 def test_default_step_makes_no_new_call(eager, monkeypatch):
-    from ubpl_amd import kernels as Kn
+    from ubpl_amd import _lib
     calls = []
-    real = Kn.call
-    monkeypatch.setattr(Kn, "call", lambda name, *a: (calls.append((name, a[0] if a else None)), real(name, *a))[1])
+    real = _lib.call
+    monkeypatch.setattr(_lib, "call", lambda name, *a: (calls.append((name, a[0] if a else None)), real(name, *a))[1])
     _one_step(*_setup(), _batches()[0])                                # no new args, viewmat in the batch or not
     names = [n for n, _ in calls]
     assert "ubpl_loss_finalize" in names
@@ -303,11 +303,11 @@ def test_batch_line_shows_the_threshold(eager):
 
 
 def test_errors_before_any_launch(eager, monkeypatch):
-    from ubpl_amd import kernels as Kn
+    from ubpl_amd import _lib
     from ubpl_amd import train as T
     calls = []
-    real = Kn.call
-    monkeypatch.setattr(Kn, "call", lambda name, *a: (calls.append(name), real(name, *a))[1])
+    real = _lib.call
+    monkeypatch.setattr(_lib, "call", lambda name, *a: (calls.append(name), real(name, *a))[1])
     views, _, meta = _batches()[0]
     on = dict(pseudoRule="uncertainty", distThrMax=4.0)
     no_mats = {k: v for k, v in meta.items() if k != "viewmat"}

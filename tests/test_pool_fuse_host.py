@@ -23,12 +23,13 @@ def _bn(C):
 
 
 def test_wrappers_refuse_mismatched_shapes_before_any_call(monkeypatch):
-    from ubpl_amd import kernels as Kn
+    from ubpl_amd import _lib, kernels as Kn
+    from ubpl_amd.kernels import _check
 
     def no_call(name, *a):
         raise AssertionError("library call %s after a bad argument" % name)
-    monkeypatch.setattr(Kn, "call", no_call)
-    monkeypatch.setattr(Kn, "_chk", no_call)
+    monkeypatch.setattr(_lib, "call", no_call)
+    monkeypatch.setattr(_check, "_chk", no_call)
     B, C, H = 2, 3, 8
     x, half, part = torch.zeros(B, C, H, H), torch.zeros(B, C, H // 2, H // 2), torch.zeros(8, dtype=torch.float64)
     v = torch.zeros(C)

@@ -1,6 +1,6 @@
 """GPU-box: out-of-bounds probe for every ubpl launch (graph-race hunt).
 
-Every device-tensor argument of every C-ABI call (kernels.call) is moved into
+Every device-tensor argument of every C-ABI call (_lib.call) is moved into
 a private copy with 64 KiB guard bands of 0xFF bytes (a NaN for f32 / bf16 /
 f64) on both sides, the op runs on the copies, the guards are checked after a
 synchronize, and the copies are written back.  A kernel that writes outside
@@ -20,7 +20,7 @@ sys.path[:0] = [os.path.join(ROOT, "ubpl-poseestimation_amd"), ROOT]
 
 import torch  # noqa: E402
 
-from ubpl_amd import kernels as Kn  # noqa: E402
+from ubpl_amd import _lib  # noqa: E402
 from ubpl_amd.hourglass import StackedHourglass  # noqa: E402
 
 GUARD = 1 << 16
@@ -109,12 +109,12 @@ def main():
     mode = sys.argv[3] if len(sys.argv) > 3 else "AvgPool"
     res = int(sys.argv[4]) if len(sys.argv) > 4 else 256
     ref = run(B, S, mode, res)
-    real = Kn.call
-    Kn.call = guarded(real)
+    real = _lib.call
+    _lib.call = guarded(real)
     try:
         got = run(B, S, mode, res)
     finally:
-        Kn.call = real
+        _lib.call = real
     names = ["preds", "feats", "grads", "stats"] if len(ref) == 4 else ["preds", "grads", "stats"]
     for nm, a, b in zip(names, ref, got):
         nan = int(torch.isnan(b).sum())
