@@ -757,6 +757,29 @@ int ubpl_augment_chain(const uint8_t* imgs, int H, int W, const int* geo, const 
 int ubpl_occlude(float* out, int V, int H, int W, const float* bank, const int64_t* off, const int* hw,
                  const int* pastes, const int* view_first, const float* chan_mean, void* stream);
 
+/* Crop from raw frames: the evaluation crop of affine_image (utils/augment.py:91-137 with
+ * angle == 0) for n boxes out of a ragged bank of uint8 BGR frames: frame f is [h][w][3] at
+ * bank + off[f], hw[2f..2f+1] = h, w.  Box b reads frame plan[16b] and writes out[b] =
+ * [3][R][R] float32, channel c = BGR channel c of u8 * (1/255.f), resampled, minus
+ * chan_mean[c].  Per axis (x: plan[16b+1..6], y: plan[16b+7..12]) the six ints
+ * (org, ls, lo, off, lb, r) state both branches of the reference as one computation:
+ *   a virtual source of ls pixels whose pixel i is frame pixel org + i (0 outside the frame);
+ *   skimage.transform.resize of it to lo pixels — a Gaussian of radius r with the weights
+ *   gauss[(2b + axis)*gw + |k|] (normalised, 0 at |k| = r + 1; ndimage 'mirror' edges, periodic),
+ *   then the bilinear sample at (g + 0.5) * ls/lo - 0.5 with mirrored indices;
+ *   a box of lb pixels of that grid from grid index off on (0 outside the grid), resized to
+ *   R pixels by the bilinear sample at (o + 0.5) * lb/R - 0.5 with mirrored indices.
+ * sf < 2: the virtual source is the integer crop box and lo = lb = R, off = 0 (the last
+ * resize is the identity); sf >= 2: the virtual source is the whole frame, lo the pre-resized
+ * size and (off, lb) the crop box in it.  Coordinates and floors in float64, weights and sums
+ * in float32, in a fixed order (no atomics).  Two passes: rows first, into inter — per box
+ * [3][rows][R] floats of which the box uses its own plan[16b+14] rows, virtual-source rows
+ * plan[16b+13] on —, then columns.  _workspace: the floats of inter. */
+int64_t ubpl_crop_frames_workspace(int n, int rows, int R);
+/*@ bank:u8[?] off:i64[?] hw:i32[?] plan:i32[16*n] gauss:f32[(int64_t)n*2*gw] chan_mean:f32[3] inter:f32[ubpl_crop_frames_workspace(n,rows,R)] out:f32[(int64_t)n*3*R*R] */
+int ubpl_crop_frames(const uint8_t* bank, const int64_t* off, const int* hw, const int* plan, const float* gauss,
+                     int gw, const float* chan_mean, int n, int rows, int R, float* inter, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,6 +62,22 @@ Predictors per view set that differ in the option alone:
 
 Same warm-up, rounds and report; off and on must agree bit for bit on every key they share
 before anything is timed.
+
+--mode frames times the crop from raw frames (ubpl_amd.frames) beside the predict call it feeds:
+per batch size (use --batches 32) and per sf = scale * 200 / res of 1, 1.5, 3 and 6, B boxes
+out of four 1080x1920 uint8 frames:
+
+  (crop)       FrameBank.crop(frame, center, scale, res), the whole call;
+  (host_plan)  frames.crop_plan alone: the per-box plan in Python, no GPU work;
+  (wrapper)    Kn.crop_frames on a plan already built: host check, two small uploads, the launches;
+  (kernels)    the ubpl_crop_frames launches alone, plan and workspace already on the device;
+  (predict)    Predictor.predict(crop, center, scale), the replay the crop feeds.
+
+Same warm-up, rounds and report; two crops must give equal bits, the launches alone must give
+the crop's bits and predict_frames must equal predict on the crop before anything is timed.  Each
+row also records the bytes the crop must move: the frame pixels under the boxes' taps, the float32
+output, and the intermediate it writes and reads once — kernels_stream_GBps says how far the HIP
+path is from streaming them, crop_stream_GBps how far the whole call is.
 """
 import argparse
 import json
@@ -246,6 +262,90 @@ def unc_main(a):
     print(line)
 
 
+FRAME_HW = (1080, 1920)
+FRAME_SFS = [1.0, 1.5, 3.0, 6.0]
+
+
+def frames_main(a):
+    """--mode frames: the crop from raw frames (FrameBank.crop: host plan + ubpl_crop_frames) and
+    the predict call it feeds, alternating, per sf = scale * 200 / res."""
+    import numpy as np
+    from ubpl_amd import Predictor, _lib, frames as F, kernels as Kn
+    _lib.require_gpu()
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    gen = torch.Generator().manual_seed(1)
+    P = Predictor(teacher(a, 0, gen, dev))
+    rs = np.random.RandomState(2)
+    ht, wd = FRAME_HW
+    bank = F.FrameBank([rs.randint(0, 256, (ht, wd, 3)).astype(np.uint8) for _ in range(4)], [0.45, 0.45, 0.45], dev)
+    R, rows = a.res, []
+    for B in [int(b) for b in a.batches.split(",")]:
+        for sf in FRAME_SFS:
+            frame = rs.randint(0, len(bank), B)
+            scale = torch.full((B,), sf * R / 200.0)
+            half = 100.0 * float(scale[0])                           # boxes inside the frame where they fit
+            center = torch.tensor(np.stack([rs.uniform(min(half, wd / 2), max(wd - half, wd / 2), B),
+                                            rs.uniform(min(half, ht / 2), max(ht - half, ht / 2), B)], 1))
+            plan = F.crop_plan(bank.sizes, frame, center, scale, R)
+
+            def span(ax, length):                                    # frame pixels one axis of a box reads
+                first, count = F._rows(tuple(int(v) for v in ax), R)
+                return max(0, min(length, int(ax[0]) + first + count) - max(0, int(ax[0]) + first))
+            src = sum(3 * span(t[1:7], wd) * span(t[7:13], ht) for t in plan.table)
+            inter = int(sum(12 * int(t[14]) * R for t in plan.table))
+            x = bank.crop(frame, center, scale, R)
+            if not torch.equal(x, bank.crop(frame, center, scale, R)):
+                raise SystemExit("predict_bench: two crops of the same boxes differ at B=%d sf=%g" % (B, sf))
+            got, want = P.predict_frames(bank, center, scale, R, frame=frame), P.predict(x, center, scale)
+            if not all(torch.equal(got[k], want[k]) for k in want):
+                raise SystemExit("predict_bench: predict_frames and predict on the crop disagree at B=%d" % B)
+            # the device part alone: the plan built, checked and uploaded once, then only the launches
+            dplan = torch.from_numpy(plan.table).to(dev)
+            dgauss = torch.from_numpy(plan.gauss.astype("float32")).to(dev)
+            gw, chunks = plan.gauss.shape[2], Kn._crop_chunks(plan.rows, R)
+            inters = [torch.empty(B * 3 * int(plan.rows[c0:c1].max()) * R, device=dev) for c0, c1 in chunks]
+            xk = torch.empty_like(x)
+
+            def kernels():
+                for (c0, c1), inter_c in zip(chunks, inters):
+                    Kn.call("ubpl_crop_frames", bank.bank, bank.off, bank.hw, dplan[c0:c1], dgauss[c0:c1], gw,
+                            bank.chan_mean, c1 - c0, int(plan.rows[c0:c1].max()), R, inter_c, xk[c0:c1])
+            kernels()
+            if not torch.equal(xk, x):
+                raise SystemExit("predict_bench: the launches alone and FrameBank.crop differ at B=%d sf=%g" % (B, sf))
+            row = {"B": B, "sf": sf, "gauss_radius": int(plan.table[:, 6].max()),
+                   "source_bytes": int(src), "output_bytes": B * 3 * R * R * 4, "intermediate_bytes": inter,
+                   "chunks": len(chunks)}
+            row.update(measure({"crop": lambda: bank.crop(frame, center, scale, R),
+                                "host_plan": lambda: F.crop_plan(bank.sizes, frame, center, scale, R),
+                                "wrapper": lambda: Kn.crop_frames(bank.bank, bank.off, bank.hw, plan.table, plan.gauss,
+                                                                  bank.chan_mean, R, out=xk,
+                                                                  layout=(bank.off_host, bank.hw_host)),
+                                "kernels": kernels,
+                                "predict": lambda: P.predict(x, center, scale)}, a))
+            # the kernels must read the source once and write the output once, and they write and
+            # read the intermediate once each
+            moved = row["source_bytes"] + row["output_bytes"] + 2 * inter
+            row["kernels_stream_GBps"] = round(moved / (row["kernels_ms"] * 1e-3) / 1e9, 1)
+            row["crop_stream_GBps"] = round(moved / (row["crop_ms"] * 1e-3) / 1e9, 2)
+            row["crop_over_predict"] = round(row["crop_ms"] / row["predict_ms"], 4)
+            rows.append(row)
+    out = {"tool": "predict_bench", "mode": "frames", "model": "HG%d" % a.stacks, "k": a.k, "res": R,
+           "frame_hw": list(FRAME_HW), "frames": len(bank), "precision": Kn.conv_precision_name(),
+           "repeats": a.repeats, "device": torch.cuda.get_device_name(0),
+           "note": "crop is FrameBank.crop end to end = host_plan (crop_plan alone) + wrapper (Kn.crop_frames on a "
+                   "built plan: host check, two small uploads, the launches); kernels is the ubpl_crop_frames "
+                   "launches alone on a plan already on the device; source_bytes are the frame pixels under the "
+                   "boxes' taps",
+           "rows": rows}
+    line = json.dumps(out)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
 def pseudo_main(a):
     from ubpl_amd import Predictor, _lib, kernels as Kn
     from ubpl_amd.hourglass import StackedHourglass
@@ -311,12 +411,14 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--window", type=float, default=0.25, help="seconds of work per variant per round")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--mode", default="predict", choices=["predict", "pseudo", "refine", "tta", "unc"])
+    ap.add_argument("--mode", default="predict", choices=["predict", "pseudo", "refine", "tta", "unc", "frames"])
     ap.add_argument("--refine", default="none", choices=["none", "quarter", "taylor"])
     ap.add_argument("--blur-sigma", type=float, default=None, help="taylor's blur (default: the Predictor's)")
     ap.add_argument("--thr", type=float, default=0.95, help="--mode pseudo: the score threshold (<= 0: each batch's median ensemble score)")
     ap.add_argument("--dist-thr", type=float, default=8.0, help="--mode unc: the distance threshold, image pixels")
     a = ap.parse_args()
+    if a.mode == "frames":
+        return frames_main(a)
     if a.mode == "unc":
         return unc_main(a)
     if a.mode == "pseudo":

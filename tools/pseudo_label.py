@@ -30,6 +30,11 @@ rows of fewer than 2 views are left out), labelled once per distance threshold (
 on the same Predictor.  --rule takes a comma-separated list, e.g. ensemble,uncertainty, to put
 the score rule beside it with the same weights and views.
 
+--frames DIR --boxes FILE.json: label one box per image of DIR instead — images of any and mixed
+sizes, read with PIL; FILE.json holds one [x, y, scale] per image (a {file name: box} object, or a
+list in the sorted order of DIR's images).  The crops are made on the device (ubpl_amd.frames);
+there is no ground truth, so only the selection is printed.  The first --rule / --refine applies.
+
 Reads tests/golden/mouse_100_500_0.3/ (tools/pack_mouse.py).  Untrained networks select
 next to nothing at the default threshold; that is the expected output without --ckpt.
 """
@@ -71,8 +76,57 @@ def tta_rows(spec, flip):
     return [(spec + (", flip" if flip else ""), views, flip)]
 
 
+def read_frames(frames_dir, boxes_file):
+    """--frames DIR --boxes FILE.json -> (names, uint8 BGR frames of any sizes, [[x, y, scale]]).
+    FILE.json: {image file name: [x, y, scale]}, or a list of [x, y, scale] for DIR's images in
+    sorted order — the box centre in pixels and the reference's scale (box side / 200)."""
+    import numpy as np
+    from PIL import Image
+    with open(boxes_file) as f:
+        boxes = json.load(f)
+    names = sorted(boxes) if isinstance(boxes, dict) else sorted(
+        n for n in os.listdir(frames_dir) if n.lower().endswith((".png", ".jpg", ".jpeg", ".bmp")))
+    rows = [boxes[n] for n in names] if isinstance(boxes, dict) else boxes
+    if len(rows) != len(names) or not names or any(len(r) != 3 for r in rows):
+        raise SystemExit("pseudo_label: %d images in %s for %d boxes of [x, y, scale]" % (len(names), frames_dir, len(rows)))
+    frames = [np.asarray(Image.open(os.path.join(frames_dir, n)).convert("RGB"), dtype=np.uint8)[:, :, ::-1].copy()
+              for n in names]
+    return names, frames, rows
+
+
+def label_frames(a, teachers, data, rules, dev):
+    """--frames: label one box per image of a directory (any image sizes) instead of the Mouse
+    split: the crops come from the device (frames.FrameBank), there is no ground truth to score."""
+    from ubpl_amd import Predictor, checkpoint
+    from ubpl_amd.frames import FrameBank
+    if not a.boxes:
+        raise SystemExit("pseudo_label: --frames needs --boxes FILE.json")
+    names, frames, rows = read_frames(a.frames, a.boxes)
+    means = data.getSemiData(100, 500, 0.3)[6]
+    bank = FrameBank(frames, means, dev)
+    center = torch.tensor([r[:2] for r in rows], dtype=torch.float64)
+    scale = torch.tensor([r[2] for r in rows], dtype=torch.float32)
+    views = tta_rows(a.tta, a.flip)[0][1]
+    rule, dist_thr = rules[0]
+    P = Predictor(teachers, flip_test=a.flip, max_batch=a.inferBS, refine=a.refine.split(",")[0], tta=views,
+                  uncertainty=rule == "uncertainty",
+                  **({} if a.blur_sigma is None else {"blur_sigma": a.blur_sigma}))
+    d = P.label_pool(bank.batches(center, scale, data.inpRes, a.inferBS), types.SimpleNamespace(outRes=data.outRes),
+                     thr=a.thr, rule=rule, dist_thr=dist_thr)
+    P.release()
+    d["source"] = {"ckpt": a.ckpt, "model": a.model, "teachers": a.teachers, "flip_test": a.flip, "frames": a.frames,
+                   "boxes": a.boxes, "images": names, "sizes": [list(s) for s in bank.sizes]}
+    checkpoint.save_pseudo_data(d, a.out)
+    print(json.dumps({"out": a.out, "images": len(names), "thr": a.thr, "rule": rule,
+                      "selected_fraction": round(float(torch.tensor(d["selected"]).float().mean()), 4),
+                      "selected_fraction_per_joint": [round(v, 4) for v in d["selected_fraction"]]}))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", default=None, help="label the images of this directory (any sizes) instead of the "
+                                                   "Mouse split; needs --boxes")
+    ap.add_argument("--boxes", default=None, help="JSON: one [x, y, scale] per image of --frames")
     ap.add_argument("--ckpt", default=None)
     ap.add_argument("--model", default="HG2")
     ap.add_argument("--teachers", type=int, default=2)
@@ -122,6 +176,8 @@ def main():
         ck = torch.load(a.ckpt, map_location="cpu", weights_only=True)
         for b, m in enumerate(teachers):
             m.load_state_dict(ck["model{}_ema_state".format(b + 1)])
+    if a.frames:
+        return label_frames(a, teachers, data, rules, dev)
     loader = mouse.valid_batches(data, a.inferBS, dev)
     if a.limit:
         loader = loader[:max(1, a.limit // a.inferBS)]

@@ -13,7 +13,8 @@ Callers use `from ubpl_amd import kernels as Kn`: the imports below are the whol
 """
 from .._lib import call  # noqa: F401
 from ._check import F32, _chk, _chk_entries, _chk_maps, _outs, _same_shape  # noqa: F401
-from .augment import _occlude_check, augment_chain, augment_warp, image_mean_u8, occlude  # noqa: F401
+from .augment import (CROP_MAX_BOXES, CROP_WORKSPACE_BYTES, _crop_chunks, _occlude_check, augment_chain,  # noqa: F401
+                      augment_warp, crop_frames, image_mean_u8, occlude)
 from .bn import (_fuse_geometry, bn_apply, bn_backward, bn_backward_pool, bn_backward_split,  # noqa: F401
                  bn_bwd_partials, bn_coeff_table, bn_eval_coeffs, bn_eval_coeffs_table, bn_forward_stats,
                  bn_forward_stats_maxpool, bn_part, bn_partial_buffer, bn_partials, bn_stats_from_partials,

@@ -101,3 +101,64 @@ def _plane(x):
     """x [B,C,...] -> (B, C, elements of one plane)."""
     B, C = x.shape[:2]
     return B, C, x[0, 0].numel()
+
+
+def _crop_plan(table, gauss, off, hw, nbank, R):
+    """Every index ubpl_crop_frames derives from a plan row stays inside its buffer: table int32
+    [n,16] and gauss [n,2,gw] (host arrays: ubpl_amd.frames.crop_plan), off / hw the host copies of
+    the bank's layout, nbank its bytes."""
+    if table.ndim != 2 or table.shape[1] != 16 or table.dtype.kind != "i" or not len(table):
+        raise ValueError("ubpl_amd: crop_frames: the plan is an int32 table [n,16], n >= 1")
+    n = len(table)
+    if gauss.ndim != 3 or gauss.shape[:2] != (n, 2) or gauss.shape[2] < 2:
+        raise ValueError("ubpl_amd: crop_frames: gauss is [n,2,gw] with gw >= 2 for %d boxes" % n)
+    t = table.astype("int64")
+    hw = hw.reshape(-1, 2).astype("int64")
+    off = off.astype("int64")
+    f = t[:, 0]
+    if len(off) != len(hw) or (f < 0).any() or (f >= len(hw)).any():
+        raise ValueError("ubpl_amd: crop_frames: a frame index outside the bank's %d frames" % len(hw))
+    if (hw < 1).any() or (off < 0).any() or (off + hw[:, 0] * hw[:, 1] * 3 > nbank).any():
+        raise ValueError("ubpl_amd: crop_frames: a frame reaches past the end of the bank")
+    for a in (1, 7):
+        org, ls, lo, o, lb, r = (t[:, a + i] for i in range(6))
+        if (ls < 1).any() or (lo < 1).any() or (lb < 1).any() or (r < 0).any() or (r + 2 > gauss.shape[2]).any() \
+                or (abs(org) + ls >= 2 ** 30).any() or (abs(o) + lb >= 2 ** 30).any():
+            raise ValueError("ubpl_amd: crop_frames: a plan row is out of range")
+    first, rows = t[:, 13], t[:, 14]
+    if (first < 0).any() or (rows < 1).any() or (first + rows > t[:, 8]).any() or int(rows.max()) * R >= 2 ** 31 \
+            or R < 1 or R * R >= 2 ** 31:
+        raise ValueError("ubpl_amd: crop_frames: a box's source rows leave its virtual source")
+    # the kernel's second pass skips a tap outside [first, first + rows) for memory safety alone: a
+    # range that misses a tap would give wrong pixels, so every tap is recomputed here
+    for i in range(n):
+        need = _crop_taps(t[i, 7:13], R)
+        if need is not None and (need[0] < first[i] or need[1] >= first[i] + rows[i]):
+            raise ValueError("ubpl_amd: crop_frames: box %d reads source rows %d..%d, its plan holds %d..%d"
+                             % (i, need[0], need[1], first[i], first[i] + rows[i] - 1))
+
+
+def _mirror(i, n):
+    """ndimage 'mirror' of index array i into [0, n), continued periodically."""
+    import numpy as np
+    if n == 1:
+        return np.zeros_like(i)
+    p = 2 * (n - 1)
+    m = np.mod(i, p)
+    return np.where(m < n, m, p - m)
+
+
+def _crop_taps(axis, R):
+    """(lowest, highest) virtual-source index any of the R outputs of one plan axis (org, ls, lo,
+    off, lb, r) taps, tap by tap as ubpl_crop_frames walks them; None when the box lies outside
+    the zoom grid."""
+    import numpy as np
+    _, ls, lo, off, lb, r = (int(v) for v in axis)
+    f = np.floor((np.arange(R) + 0.5) * (lb / R) - 0.5).astype(np.int64)
+    g = off + np.concatenate([_mirror(f, lb), _mirror(f + 1, lb)])
+    g = np.unique(g[(g >= 0) & (g < lo)])
+    if not g.size:
+        return None
+    fq = np.floor((g + 0.5) * (ls / lo) - 0.5).astype(np.int64)
+    idx = _mirror(fq[:, None] + np.arange(-r, r + 2)[None, :], ls)
+    return int(idx.min()), int(idx.max())

@@ -1,5 +1,5 @@
-"""Device augmentation (f1): image means, the view warps and the occlusion pastes, with the
-host checks of their small tables."""
+"""Device augmentation (f1): image means, the view warps, the occlusion pastes and the
+evaluation crop from raw frames, with the host checks of their small tables."""
 import torch
 
 from .. import _lib
@@ -57,6 +57,51 @@ def augment_chain(imgs, geo, cs, noise, img_mean, chan_mean, Hm, Wm, out):
     inter = torch.empty((V, 3, Hm, Wm), device=out.device, dtype=F32)
     _lib.call("ubpl_augment_chain", imgs, imgs.shape[1], imgs.shape[2], geo, cs, noise, img_mean, chan_mean, V, int(Hm),
               int(Wm), inter, Ho, Wo, out)
+    return out
+
+
+CROP_WORKSPACE_BYTES = 256 << 20
+CROP_MAX_BOXES = 65535          # boxes of one ubpl_crop_frames launch (the box is the grid's y index)
+
+
+def _crop_chunks(rows, R, budget=None):
+    """[(first box, end box)] such that a chunk's intermediate — boxes x 3 x (its largest row
+    count) x R floats — stays within budget bytes (default CROP_WORKSPACE_BYTES; a single box
+    may exceed it) and a chunk holds at most CROP_MAX_BOXES boxes."""
+    budget = CROP_WORKSPACE_BYTES if budget is None else budget
+    chunks, a, top = [], 0, 0
+    for i, r in enumerate(rows):
+        if i > a and ((i + 1 - a) * 12 * max(top, int(r)) * R > budget or i - a >= CROP_MAX_BOXES):
+            chunks.append((a, i))
+            a, top = i, 0
+        top = max(top, int(r))
+    return chunks + [(a, len(rows))]
+
+
+def crop_frames(bank, off, hw, table, gauss, chan_mean, res, out=None, layout=None):
+    """The reference's evaluation crop of n boxes out of a ragged uint8 BGR frame bank (see
+    frame_crop.hip): bank / off / hw on the device (frame f is [h,w,3] at bank + off[f]); table
+    int32 [n,16] and gauss [n,2,gw] the HOST plan of ubpl_amd.frames.crop_plan; out float32
+    [n,3,res,res].  layout: host copies of (off, hw) for the bounds check (else read back).
+    The boxes run in chunks whose intermediate stays within CROP_WORKSPACE_BYTES."""
+    _check._chk(bank, "bank", torch.uint8)
+    _check._chk(off, "off", torch.int64)
+    _check._chk(hw, "hw", torch.int32)
+    _check._chk(chan_mean, "chan_mean")
+    R = int(res)
+    off_h, hw_h = layout if layout is not None else (off.cpu().numpy(), hw.cpu().numpy())
+    _check._crop_plan(table, gauss, off_h, hw_h, bank.numel(), R)
+    n, gw = gauss.shape[0], gauss.shape[2]
+    if out is None:
+        out = torch.empty((n, 3, R, R), device=bank.device, dtype=F32)
+    _check._chk(out, "out")
+    _check._same_shape("out", out, (n, 3, R, R))
+    plan = torch.from_numpy(table.astype("int32")).to(bank.device)
+    g = torch.from_numpy(gauss.astype("float32")).to(bank.device)
+    for a, e in _crop_chunks(table[:, 14], R):
+        rows = int(table[a:e, 14].max())
+        inter = torch.empty(int(_lib.lib().ubpl_crop_frames_workspace(e - a, rows, R)), device=bank.device, dtype=F32)
+        _lib.call("ubpl_crop_frames", bank, off, hw, plan[a:e], g[a:e], gw, chan_mean, e - a, rows, R, inter, out[a:e])
     return out
 
 

@@ -297,6 +297,29 @@ class Predictor:
         out_res: the resolution of the inverse transform (default: the heatmaps')."""
         return self._chunked("predict", imgs, center, scale, out_res, pseudo=False, want_hm=bool(return_heatmaps))
 
+    # -- from raw frames ---------------------------------------------------
+    def _crop(self, bank, center, scale, frame, res):
+        """The boxes of a frames.FrameBank as network inputs [n,3,res,res]: the
+        reference's evaluation crop (ubpl_crop_frames), run eagerly on the current stream ahead
+        of the replay — frame sizes vary, so it is no part of a captured graph."""
+        if bank.bank.device != self.device:
+            raise ValueError("ubpl_amd: the FrameBank lives on %s, the networks on %s"
+                             % (bank.bank.device, self.device))
+        with torch.cuda.device(self.device), torch.no_grad():
+            return bank.crop(frame, center, scale, res)
+
+    def predict_frames(self, bank, center, scale, res, frame=None, **predict_kwargs):
+        """predict on boxes of raw frames: bank a frames.FrameBank (uint8 BGR frames of any
+        sizes), box i = (frame[i], center[i] = (x, y), scale[i]) with frame None meaning box i
+        of frame i, res the side of the networks' input (required: a Predictor serves any input
+        size, so there is none to default to).  The result is predict's on
+        bank.crop(frame, center, scale, res) with the same center / scale, bit for bit."""
+        return self.predict(self._crop(bank, center, scale, frame, res), center, scale, **predict_kwargs)
+
+    def pseudo_label_frames(self, bank, center, scale, res, frame=None, **pseudo_kwargs):
+        """pseudo_label on boxes of raw frames (see predict_frames)."""
+        return self.pseudo_label(self._crop(bank, center, scale, frame, res), center, scale, **pseudo_kwargs)
+
     # -- ensemble pseudo-labels --------------------------------------------
     def pseudo_label(self, imgs, center=None, scale=None, thr=0.95, rule="unanimous", return_heatmaps=False,
                      out_res=None, dist_thr=None):
