@@ -82,8 +82,8 @@ def test_gate_of_ones_is_kind_2(thr):
         assert _bits_equal(a, b) if a.dtype.is_floating_point else torch.equal(a, b), name
     # out_w as well: the backward's row weights
     from ubpl_amd import kernels as Kn
-    g = Kn.geom_stack(d["preds"].to(DEV), t, S, "ens")
-    sq, am, tm = Kn.row_stats(g, want_amax=True, want_tmax=True)
+    rows = Kn.RowSpec.ensemble(B, S, K, R * R, M, t.shape[2])
+    sq, am, tm = Kn.row_stats(d["preds"].to(DEV), t, rows, want_amax=True, want_tmax=True)
     w2 = Kn.loss_finalize(2, sq, am, tm, None, sw, False, True, B, S, K, thr)[3]
     w3 = Kn.loss_finalize(3, sq, am, tm, ones, sw, False, True, B, S, K, thr)[3]
     assert _bits_equal(w2, w3) and float(w2.sum()) > 0

@@ -150,14 +150,19 @@ def test_threshold_nans_order_last_and_limits():
 
 
 def _finalize_statement(kind, sq, asc, tsc, athr, tthr, gate, sw, use_gate, use_sw, B, S, K):
-    """ubpl_loss_finalize_ranked in numpy, per row in float32 as the kernel, the sum in float64."""
+    """The finalize entries in numpy, per row in float32 as the kernel, the sum in float64: kinds 1
+    and 2 as ubpl_loss_finalize_ranked takes them (per-stack thresholds), and with athr = tthr = one
+    constant repeated, kinds 0 to 3 of ubpl_loss_finalize (asc = amax, tsc = tmax).  Kind 3 is kind 2
+    with [gate > 0] in the mask and the gate out of cnt[0]."""
     sq, tsc = sq.reshape(B, S, K), tsc.reshape(B, S, K)
     g = np.ones((B, 1, K), np.float32) if gate is None else gate.reshape(B, 1, K)
     w = np.ones((B, 1, 1), np.float32) if sw is None else sw.reshape(B, 1, 1)
-    m = (tsc >= tthr.reshape(1, S, 1)).astype(np.float32)
-    if kind == 2:
+    m = np.ones((B, S, K), np.float32) if kind == 0 else (tsc >= tthr.reshape(1, S, 1)).astype(np.float32)
+    if kind >= 2:
         l = sq * w
         m = m * (asc.reshape(B, S, K) >= athr.reshape(1, S, 1)).astype(np.float32)
+        if kind == 3:
+            m = m * (g > 0).astype(np.float32)
         wv = m * w
     else:
         l, wv = sq, m
@@ -168,9 +173,81 @@ def _finalize_statement(kind, sq, asc, tsc, athr, tthr, gate, sw, use_gate, use_
     rows = (w.reshape(B) > 0)
     n_rows = int(rows.sum())
     st = tsc[rows].sum(0) / max(n_rows, 1)
-    score = ((asc.reshape(B, S, K)[rows].sum(0) / max(n_rows, 1) + st) / 2 if kind == 2 else st).mean(0)
-    cnt = [S * int((g > 0).sum()), int((l > 0).sum()), int((m > 0).sum()), n_rows]
+    score = ((asc.reshape(B, S, K)[rows].sum(0) / max(n_rows, 1) + st) / 2 if kind >= 2 else st).mean(0)
+    n_gate = B * K if kind == 3 else int((g > 0).sum())
+    cnt = [S * n_gate, int((l > 0).sum()), int((m > 0).sum()), n_rows]
     return float((l * m).astype(np.float64).sum()), cnt, score, np.broadcast_to(wv, (B, S, K)).reshape(-1)
+
+
+def _finalize_inputs(seed):
+    """B = 5, S = 3, K = 17 (odd against the 256-thread row loop, K > 16): sq_mean with zero rows,
+    two score sets with a NaN, gate with zeros, sw with zeros."""
+    B, S, K = 5, 3, 17
+    rs = np.random.RandomState(seed)
+    sq = rs.uniform(0.0, 1.0, B * S * K).astype(np.float32)
+    sq[::11] = 0.0
+    asc, tsc = (rs.uniform(0.05, 0.15, B * S * K).astype(np.float32) for _ in range(2))
+    tsc[7] = np.nan                                                     # a NaN score never selects
+    gate = (rs.uniform(size=(B, K)) > 0.3).astype(np.float32) * 1.5
+    sw = np.array([0.0, 1.0, 0.5, 0.0, 2.0], np.float32)
+    return B, S, K, rs, sq, asc, tsc, gate, sw
+
+
+def _dv(a):
+    return None if a is None else torch.from_numpy(a).to(DEV)
+
+
+# (gate, sw, use_gate, use_sw) by name: what test_finalize_against_the_statement lists per kind
+_COMBOS_GATED = (("gate", "sw", 1, 1), ("gate", "sw", 0, 0), (None, None, 1, 1), ("gate", "sw", 1, 0))
+_COMBOS_PSEUDO = ((None, "sw", 0, 1),)
+
+
+@pytest.mark.parametrize("kind", [0, 1, 2, 3])
+def test_finalize_constant_threshold_against_the_statement(kind):
+    """ubpl_loss_finalize, all four kinds, against the numpy statement: counts and out_w exact, sum
+    and score to the file's 1e-4 relative bar."""
+    from ubpl_amd import kernels as Kn
+    B, S, K, _, sq, amax, tmax, gate, sw = _finalize_inputs(11 + kind)
+    thr = float(tmax[K + 3])                                            # a threshold that is a score: >= keeps it
+    thrs = np.full(S, thr, np.float32)
+    combos = _COMBOS_GATED if kind < 2 else (_COMBOS_PSEUDO if kind == 2 else (("gate", "sw", 0, 1),))
+    for gn, wn, ug, us in combos:
+        g, w = (gate if gn else None), (sw if wn else None)
+        want = _finalize_statement(kind, sq, amax, tmax, thrs, thrs, g, w, ug, us, B, S, K)
+        s, cnt, score, wv = Kn.loss_finalize(kind, _dv(sq), _dv(amax) if kind >= 2 else None,
+                                             _dv(tmax) if kind else None, _dv(g), _dv(w), ug, us, B, S, K, thr)
+        print("kind %d gate %s sw %s use %d %d: cnt %s want %s, sum %.9g want %.9g"
+              % (kind, gn, wn, ug, us, cnt.tolist(), want[1], float(s), want[0]))
+        assert cnt.tolist() == want[1]
+        assert np.array_equal(wv.cpu().numpy(), want[3])
+        assert abs(float(s) - want[0]) <= 1e-4 * abs(want[0])
+        if kind == 0:
+            assert score is None
+        else:
+            assert np.allclose(score.cpu().numpy(), want[2], rtol=1e-4, atol=0, equal_nan=True)
+            assert np.isnan(want[2]).sum() == (1 if w is None else 0)
+        assert 0 < want[1][2] and (kind == 0 or want[1][2] < B * S * K)      # the mask is neither empty nor full
+
+
+@pytest.mark.parametrize("kind", [1, 2])
+def test_finalize_and_finalize_ranked_give_the_same_bits(kind):
+    """One finalize body serves both entries: ubpl_loss_finalize on (amax, tmax, thr) and
+    ubpl_loss_finalize_ranked on the same arrays as scores with thr repeated per stack agree in
+    every output bit."""
+    from ubpl_amd import kernels as Kn
+    B, S, K, _, sq, amax, tmax, gate, sw = _finalize_inputs(21 + kind)
+    thr = float(tmax[K + 3])
+    thrs = _dv(np.full(S, thr, np.float32))
+    for gn, wn, ug, us in (_COMBOS_GATED if kind == 1 else _COMBOS_PSEUDO):
+        g, w = _dv(gate if gn else None), _dv(sw if wn else None)
+        a_in = _dv(amax) if kind == 2 else None
+        one = Kn.loss_finalize(kind, _dv(sq), a_in, _dv(tmax), g, w, ug, us, B, S, K, thr)
+        two = Kn.loss_finalize_ranked(kind, _dv(sq), a_in, _dv(tmax), thrs if kind == 2 else None, thrs, g, w, ug, us,
+                                      B, S, K)
+        assert int(one[1][2]) > 0
+        for name, a, b in zip(("sum", "cnt", "score", "w"), one, two):
+            assert a.dtype == b.dtype and a.shape == b.shape, name
+            assert torch.equal(a.view(torch.int32), b.view(torch.int32)), (name, a, b)
 
 
 @pytest.mark.parametrize("kind", [1, 2])

@@ -8,28 +8,15 @@
 //   row_stats  one workgroup per row: sum of squares, max of a, max of the
 //              (model-averaged) target, in one HBM pass;
 //   finalize   one workgroup per loss: weights, mask, sum and every count on
-//              device (no host sync);
+//              device (no host sync) — the body is finalize_rows in loss_rows.h,
+//              shared with loss_rate.hip's two finalize entries;
 //   row_grad   d/da = w_row * g * 2 (a - t) / HW written (or accumulated) in
 //              one pass, g read from device memory (autograd's grad_output).
 // Row geometry is given by strides so that stack slices ([:, -1]) and teacher
 // stacks ([M, B, S, K, R, R]) are consumed in place, without copies.
-#include "common.h"
+#include "loss_rows.h"
 
 namespace {
-
-struct RowGeom {
-    const float* a;
-    int64_t a_sb, a_ss;  // a row (b,s,k) at a + b*a_sb + s*a_ss + k*HW
-    const float* t;
-    int64_t t_sb, t_ss, t_sm;  // target row (b,s,k) = mean over m of t + m*t_sm + b*t_sb + s*t_ss + k*HW
-    int M;
-};
-
-__device__ __forceinline__ float target_at(const RowGeom& g, const float* trow, int64_t i) {
-    float acc = trow[i];
-    for (int m = 1; m < g.M; ++m) acc += trow[(int64_t)m * g.t_sm + i];
-    return g.M == 1 ? acc : acc / (float)g.M;
-}
 
 __global__ void __launch_bounds__(256) row_stats_kernel(RowGeom g, int S, int K, int HW, float* __restrict__ sq_mean,
                                                        float* __restrict__ amax, float* __restrict__ tmax) {
@@ -41,7 +28,7 @@ __global__ void __launch_bounds__(256) row_stats_kernel(RowGeom g, int S, int K,
     float sq = 0.f, am = -INFINITY, tm = -INFINITY;
     for (int i = threadIdx.x; i < HW; i += blockDim.x) {
         const float av = arow[i];
-        const float tv = target_at(g, trow, i);
+        const float tv = member_mean(trow + i, g.t_sm, g.M);
         const float d = av - tv;
         sq = fmaf(d, d, sq);
         am = fmaxf(am, av);
@@ -74,18 +61,12 @@ __global__ void __launch_bounds__(256) row_grad_kernel(RowGeom g, int S, int K, 
     const float* arow = g.a + off;
     const float* trow = g.t + b * g.t_sb + s * g.t_ss + (int64_t)k * HW;
     for (int i = threadIdx.x; i < HW; i += blockDim.x) {
-        const float v = c * (arow[i] - target_at(g, trow, i));
+        const float v = c * (arow[i] - member_mean(trow + i, g.t_sm, g.M));
         drow[i] = accumulate ? drow[i] + v : v;
     }
 }
 
-// kind 0: MSE / consistency   w = gate? * sw?                     (utils/losses.py:16-53)
-// kind 1: teacher-confidence  w = gate? * sw? * [tmax >= thr]     (utils/losses.py:255-286)
-// kind 2: UBPL pseudo mask    w = sw * [amax >= thr] * [tmax >= thr]  (utils/losses.py:176-210)
-// kind 3: kind 2 with a given selection: w = sw * [gate > 0] * [amax >= thr] * [tmax >= thr]; the
-//         gate [B,K] is a row mask only (cnt[0] stays kind 2's S*B*K)
-// cnt[0] = S * #{gate > 0}, cnt[1] = n_pseudo = #{pre-mask loss > 0},
-// cnt[2] = n_sel = #{mask > 0}, cnt[3] = #{rows with sw > 0}.
+// The per-map maxima of row_stats against one scalar threshold (finalize_rows, loss_rows.h).
 __global__ void __launch_bounds__(256) finalize_kernel(int kind, const float* __restrict__ sq_mean,
                                                       const float* __restrict__ amax,
                                                       const float* __restrict__ tmax,
@@ -93,74 +74,8 @@ __global__ void __launch_bounds__(256) finalize_kernel(int kind, const float* __
                                                       int use_gate, int use_sw, int B, int S, int K, float thr,
                                                       float* __restrict__ out_sum, int* __restrict__ out_cnt,
                                                       float* __restrict__ out_score, float* __restrict__ out_w) {
-    __shared__ double dred[16];
-    __shared__ int ired[16];
-    const int rows = B * S * K;
-    double lsum = 0.0;
-    int n_pos = 0, n_sel = 0, n_gate = 0;
-    for (int r = threadIdx.x; r < rows; r += blockDim.x) {
-        const int k = r % K, b = r / (K * S);
-        const float gv = gate ? gate[b * K + k] : 1.f;
-        const float sv = sw ? sw[b] : 1.f;
-        float l = sq_mean[r];
-        float m = 1.f;
-        if (kind == 2) {
-            if (sw) l = l * sv;
-            m = (amax[r] >= thr ? 1.f : 0.f) * (tmax[r] >= thr ? 1.f : 0.f);
-        } else if (kind == 3) {
-            if (sw) l = l * sv;
-            m = (gv > 0.f ? 1.f : 0.f) * (amax[r] >= thr ? 1.f : 0.f) * (tmax[r] >= thr ? 1.f : 0.f);
-        } else {
-            if (use_gate) l = l * gv;
-            if (use_sw && sw) l = l * sv;
-            if (kind == 1) m = tmax[r] >= thr ? 1.f : 0.f;
-        }
-        n_pos += l > 0.f;
-        n_sel += m > 0.f;
-        lsum += (double)(l * m);
-        float wv = m;
-        if (kind == 2 || kind == 3) {
-            if (sw) wv *= sv;
-        } else {
-            if (use_gate) wv *= gv;
-            if (use_sw && sw) wv *= sv;
-        }
-        out_w[r] = wv;
-    }
-    for (int r = threadIdx.x; r < B * K; r += blockDim.x) n_gate += (gate && kind != 3 ? gate[r] : 1.f) > 0.f;
-    lsum = ubpl::block_sum(lsum, dred);
-    n_pos = ubpl::block_sum(n_pos, ired);
-    n_sel = ubpl::block_sum(n_sel, ired);
-    n_gate = ubpl::block_sum(n_gate, ired);
-    int n_rows = 0;
-    for (int b = 0; b < B; ++b) n_rows += (sw ? sw[b] : 1.f) > 0.f;
-    if (threadIdx.x == 0) {
-        out_sum[0] = (float)lsum;
-        out_cnt[0] = S * n_gate;
-        out_cnt[1] = n_pos;
-        out_cnt[2] = n_sel;
-        out_cnt[3] = n_rows;
-    }
-    // per-keypoint confidence score over rows with sw > 0 (utils/losses.py:196-208, :275-285)
-    if (out_score != nullptr && kind != 0) {
-        for (int k = threadIdx.x; k < K; k += blockDim.x) {
-            float acc_s = 0.f;
-            for (int s = 0; s < S; ++s) {
-                float sa = 0.f, st = 0.f;
-                for (int b = 0; b < B; ++b) {
-                    if ((sw ? sw[b] : 1.f) > 0.f) {
-                        const int r = (b * S + s) * K + k;
-                        if (kind >= 2) sa += amax[r];
-                        st += tmax[r];
-                    }
-                }
-                const float ma = n_rows > 0 ? sa / (float)n_rows : 0.f;
-                const float mt = n_rows > 0 ? st / (float)n_rows : 0.f;
-                acc_s += kind >= 2 ? (ma + mt) / 2.f : mt;
-            }
-            out_score[k] = acc_s / (float)S;
-        }
-    }
+    finalize_rows(kind, sq_mean, amax, tmax, S, ThrConst{thr}, ThrConst{thr}, gate, sw, use_gate, use_sw, B, S, K,
+                  out_sum, out_cnt, out_score, out_w);
 }
 
 // ---------------------------------------------------------------- FDL (L5)

@@ -10,11 +10,13 @@
 //                  combined by an integer atomic max on the scores' bits (they are >= 0, so
 //                  the bit order is the value order, and max is order-independent);
 //   rank_select    one workgroup per group: the rank-th smallest by counting (no sort);
-//   finalize       loss.hip's finalize for kinds 1 and 2 with the scores given and the
-//                  thresholds read per stack from device memory;
-//   finalize_rank  the step's form: the rank selections folded into the finalize launch.
+//   finalize       the shared finalize body (finalize_rows, loss_rows.h) for kinds 1 and 2 with
+//                  the scores given and the thresholds read per stack from device memory;
+//   finalize_rank  the step's form: the rank selections folded into the finalize launch, the
+//                  same body reading its thresholds from LDS.
+// The member mean of an ensemble target is loss_rows.h's member_mean, as in loss.hip's kernels.
 // The mask carries no gradient, so ubpl_heatmap_row_grad serves the backward with out_w.
-#include "common.h"
+#include "loss_rows.h"
 
 namespace {
 
@@ -34,7 +36,6 @@ __global__ void __launch_bounds__(256) softmax_peak_kernel(const float* __restri
     const int bs = blockIdx.y, b = bs / S, s = bs % S;
     const float* base = x + b * x_sb + s * x_ss;
     const int p0 = blockIdx.x * per, p1 = min(p0 + per, HW);
-    const float fm = (float)M;
     float best[KT];
 #pragma unroll
     for (int k = 0; k < KT; ++k) best[k] = 0.f;
@@ -44,10 +45,7 @@ __global__ void __launch_bounds__(256) softmax_peak_kernel(const float* __restri
 #pragma unroll
         for (int k = 0; k < KT; ++k) {
             if (k < K) {
-                const float* row = base + (int64_t)k * HW + i;
-                float acc = row[0];
-                for (int m = 1; m < M; ++m) acc += row[(int64_t)m * x_sm];   // member order, as target_at
-                v[k] = M == 1 ? acc : acc / fm;
+                v[k] = member_mean(base + (int64_t)k * HW + i, x_sm, M);
                 mx = fmaxf(mx, v[k]);
             }
         }
@@ -131,85 +129,7 @@ __global__ void __launch_bounds__(RANK_NT) rank_select_kernel(const float* __res
     select_rank(scores + (int64_t)blockIdx.x * N, N, 0, N, rank, keys, thr + blockIdx.x);
 }
 
-// loss.hip finalize_kernel for kinds 1 and 2, the scores given and the thresholds per stack
-// (athr, tthr: global or LDS).  tscore holds TS stacks: S, or 1 when one target map serves
-// every stack (then tthr[s] is read for every s all the same).  Any block size finalize_kernel takes.
-__device__ __forceinline__ void finalize_ranked_body(int kind, const float* __restrict__ sq_mean,
-                                                     const float* __restrict__ ascore,
-                                                     const float* __restrict__ tscore, int TS, const float* athr,
-                                                     const float* tthr, const float* __restrict__ gate,
-                                                     const float* __restrict__ sw, int use_gate, int use_sw, int B,
-                                                     int S, int K, float* __restrict__ out_sum,
-                                                     int* __restrict__ out_cnt, float* __restrict__ out_score,
-                                                     float* __restrict__ out_w) {
-    __shared__ double dred[16];
-    __shared__ int ired[16];
-    const int rows = B * S * K;
-    double lsum = 0.0;
-    int n_pos = 0, n_sel = 0, n_gate = 0;
-    for (int r = threadIdx.x; r < rows; r += blockDim.x) {
-        const int k = r % K, s = (r / K) % S, b = r / (K * S);
-        const float gv = gate ? gate[b * K + k] : 1.f;
-        const float sv = sw ? sw[b] : 1.f;
-        float l = sq_mean[r];
-        float m = tscore[TS == 1 ? b * K + k : r] >= tthr[s] ? 1.f : 0.f;
-        float wv;
-        if (kind == 2) {
-            if (sw) l = l * sv;
-            m *= ascore[r] >= athr[s] ? 1.f : 0.f;
-            wv = sw ? m * sv : m;
-        } else {
-            wv = m;
-            if (use_gate) {
-                l = l * gv;
-                wv *= gv;
-            }
-            if (use_sw && sw) {
-                l = l * sv;
-                wv *= sv;
-            }
-        }
-        n_pos += l > 0.f;
-        n_sel += m > 0.f;
-        lsum += (double)(l * m);
-        out_w[r] = wv;
-    }
-    for (int r = threadIdx.x; r < B * K; r += blockDim.x) n_gate += (gate ? gate[r] : 1.f) > 0.f;
-    lsum = ubpl::block_sum(lsum, dred);
-    n_pos = ubpl::block_sum(n_pos, ired);
-    n_sel = ubpl::block_sum(n_sel, ired);
-    n_gate = ubpl::block_sum(n_gate, ired);
-    int n_rows = 0;
-    for (int b = 0; b < B; ++b) n_rows += (sw ? sw[b] : 1.f) > 0.f;
-    if (threadIdx.x == 0) {
-        out_sum[0] = (float)lsum;
-        out_cnt[0] = S * n_gate;
-        out_cnt[1] = n_pos;
-        out_cnt[2] = n_sel;
-        out_cnt[3] = n_rows;
-    }
-    // per-keypoint mean score over rows with sw > 0 (utils/losses.py:152-159)
-    if (out_score != nullptr) {
-        for (int k = threadIdx.x; k < K; k += blockDim.x) {
-            float acc_s = 0.f;
-            for (int s = 0; s < S; ++s) {
-                float sa = 0.f, st = 0.f;
-                for (int b = 0; b < B; ++b) {
-                    if ((sw ? sw[b] : 1.f) > 0.f) {
-                        const int r = (b * S + s) * K + k;
-                        if (kind == 2) sa += ascore[r];
-                        st += tscore[TS == 1 ? b * K + k : r];
-                    }
-                }
-                const float ma = n_rows > 0 ? sa / (float)n_rows : 0.f;
-                const float mt = n_rows > 0 ? st / (float)n_rows : 0.f;
-                acc_s += kind == 2 ? (ma + mt) / 2.f : mt;
-            }
-            out_score[k] = acc_s / (float)S;
-        }
-    }
-}
-
+// finalize_rows (loss_rows.h) for kinds 1 and 2 with the scores given and the thresholds per stack.
 __global__ void __launch_bounds__(256) finalize_ranked_kernel(int kind, const float* __restrict__ sq_mean,
                                                              const float* __restrict__ ascore,
                                                              const float* __restrict__ tscore,
@@ -220,8 +140,8 @@ __global__ void __launch_bounds__(256) finalize_ranked_kernel(int kind, const fl
                                                              int B, int S, int K, float* __restrict__ out_sum,
                                                              int* __restrict__ out_cnt, float* __restrict__ out_score,
                                                              float* __restrict__ out_w) {
-    finalize_ranked_body(kind, sq_mean, ascore, tscore, S, athr, tthr, gate, sw, use_gate, use_sw, B, S, K, out_sum,
-                         out_cnt, out_score, out_w);
+    finalize_rows(kind, sq_mean, ascore, tscore, S, athr, tthr, gate, sw, use_gate, use_sw, B, S, K, out_sum, out_cnt,
+                  out_score, out_w);
 }
 
 constexpr int RANK_MAX_STACKS = 16;
@@ -250,8 +170,9 @@ __global__ void __launch_bounds__(RANK_NT) finalize_rank_kernel(int kind, const 
     if (TS == 1 && threadIdx.x > 0 && (int)threadIdx.x < S) thr_s[S + threadIdx.x] = thr_s[S];
     __syncthreads();
     if ((int)threadIdx.x < 2 * S) thr[threadIdx.x] = thr_s[threadIdx.x];
-    finalize_ranked_body(kind, sq_mean, ascore, tscore, TS, thr_s, thr_s + S, gate, sw, use_gate, use_sw, B, S, K,
-                         out_sum, out_cnt, out_score, out_w);
+    const float* athr = thr_s;
+    finalize_rows(kind, sq_mean, ascore, tscore, TS, athr, athr + S, gate, sw, use_gate, use_sw, B, S, K, out_sum,
+                  out_cnt, out_score, out_w);
 }
 
 }  // namespace

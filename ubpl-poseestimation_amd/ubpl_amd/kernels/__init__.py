@@ -32,10 +32,9 @@ from .optim import (adamw_ema_step_dev_, adamw_ema_step_guarded_dev_, adamw_step
                     adamw_step_guarded_dev_, ema_update_, grad_guard_, grad_guard_scratch, restore_if_, scale_)
 from .pool import (add, avgpool2x2, avgpool2x2_backward, maxpool2x2, maxpool2x2_backward, stats_ok,  # noqa: F401
                    upsample2x_add, upsample2x_add_backward)
-from .render_loss import (MAX_RANK_GROUP, MAX_SCORE_MAPS, MAX_SCORE_MEMBERS, RowGeom, fdl_cov_backward,  # noqa: F401
-                          fdl_cov_forward, geom_rows, geom_stack, loss_finalize, loss_finalize_rank,
-                          loss_finalize_ranked, rank_threshold, render_heatmaps, row_grad, row_stats,
-                          softmax_peak_scores)
+from .render_loss import (MAX_RANK_GROUP, MAX_SCORE_MAPS, MAX_SCORE_MEMBERS, RowSpec, fdl_cov_backward,  # noqa: F401
+                          fdl_cov_forward, loss_finalize, loss_finalize_rank, loss_finalize_ranked, pred_rows,
+                          rank_threshold, render_heatmaps, row_grad, row_stats, softmax_peak_scores)
 from .split_operands import (CONV_PRECISIONS, DEFAULT_CONV_PRECISION, SplitAct, SplitWeights,  # noqa: F401
                              backward_pieces, conv_precision_name, conv_precision_pieces)
 from .view_geometry import (F64, MAX_VIEWS, _about_centre, _mat6, affine_pixels_to_theta,  # noqa: F401

@@ -1,5 +1,7 @@
 """Heatmap rendering (R1) and the loss kernels (L1-L5): row statistics, the selection rules'
 finalizes, row gradients and the feature covariance loss."""
+from typing import NamedTuple
+
 import torch
 
 from .. import _lib
@@ -23,58 +25,86 @@ def render_heatmaps(kps, img_hw, inp_res, out_res, kernel_size=3.0, sigma=1.0, c
 
 
 # ------------------------------------------------------------------ L1-L4
-class RowGeom:
-    """Row geometry of a (pred, target) pair for the heatmap loss kernels.
-    a rows (b,s,k): a + b*a_sb + s*a_ss + k*HW; target rows: mean over m of
-    t + m*t_sm + b*t_sb + s*t_ss + k*HW (strides in elements)."""
+class RowSpec(NamedTuple):
+    """Rows of a (pred, target) pair for the heatmap loss kernels, in elements.  The predictions
+    are contiguous [B,S,K,HW]: row (b,s,k) at (b*S + s)*K*HW + k*HW.  Its target is the mean over
+    m < M of the maps at base + m*t_sm + b*t_sb + s*t_ss + k*HW of the flat target tensor.  The
+    constructors below are the layouts that exist, and the only place a target stride is
+    multiplied out: a wrong one reads valid memory of the wrong map, which nothing downstream
+    can notice."""
+    B: int
+    S: int
+    K: int
+    HW: int
+    t_sb: int
+    t_ss: int
+    t_sm: int
+    M: int
+    base: int
 
-    def __init__(self, a, a_sb, a_ss, t, t_sb, t_ss, t_sm, M, B, S, K, HW):
-        self.a, self.t = a, t
-        self.a_off = 0
-        self.args = (a_sb, a_ss, t_sb, t_ss, t_sm, M, B, S, K, HW)
-        self.B, self.S, self.K, self.HW = B, S, K, HW
-        self.a_ptr = a          # row base pointers as tensors (views at an element offset)
-        self.t_ptr = t
+    @classmethod
+    def ground_truth(cls, B, S, K, HW):
+        """t [B,K,HW]: one map per (b,k), broadcast over the stacks."""
+        return cls(B, S, K, HW, K * HW, 0, 0, 1, 0)
+
+    @classmethod
+    def same(cls, B, S, K, HW):
+        """t [B,S,K,HW]: the predictions' own layout, stack by stack."""
+        return cls(B, S, K, HW, S * K * HW, K * HW, 0, 1, 0)
+
+    @classmethod
+    def ensemble(cls, B, S, K, HW, M, St=1):
+        """t [M,B,St,K,HW] (or [M,B,K,HW], St = 1): the member mean of the LAST stack, for every
+        stack of the predictions."""
+        return cls(B, S, K, HW, St * K * HW, 0, B * St * K * HW, M, (St - 1) * K * HW)
+
+    @classmethod
+    def flat(cls, B, C, HW):
+        """a and t [B,C,HW] (the feature-distance loss): row (b,c) against row (b,c)."""
+        return cls(B, 1, C, HW, C * HW, 0, 0, 1, 0)
+
+    @property
+    def a_sb(self):
+        return self.S * self.K * self.HW
+
+    @property
+    def a_ss(self):
+        return self.K * self.HW
+
+    @property
+    def t_stacks(self):
+        """Stacks of distinct target rows: S, or 1 when one map per (b,k) serves every stack."""
+        return 1 if self.t_ss == 0 else self.S
+
+    def target(self, t):
+        """The flat view of t at the base element: what the kernels take as the target pointer."""
+        return t.reshape(-1)[self.base:]
 
 
-def geom_stack(a, t, S, t_mode):
-    """a: [B,S,K,R,R] (or [B,K,R,R] with S==1), contiguous.
-    t_mode 'gt'    t [B,K,R,R] broadcast over stacks;
-           'same'  t has a's layout;
-           'ens'   t [M,B,St,K,R,R] (or [M,B,K,R,R]): mean over M of the LAST stack."""
+def pred_rows(preds, nstack):
+    """(B, S, K, HW) of the reference's reshape((bs, k, -1)) per stack (utils/losses.py:20-23):
+    with nStack == 1 a row is (sample, preds.size(1)) — for a [B,1,K,R,R] model output that is
+    ONE row per sample over K*R*R pixels."""
+    B = preds.shape[0]
+    if nstack == 1:
+        K = preds.shape[1]
+        return B, 1, K, preds.numel() // (B * K)
+    K = preds.shape[2]
+    return B, nstack, K, preds.numel() // (B * nstack * K)
+
+
+def row_stats(a, t, rows, want_amax=False, want_tmax=False):
+    """Per row of a against its target (rows: a RowSpec): the pixel mean of the squared
+    difference, and where wanted the maxima of the row and of its target."""
     _check._chk(a, "preds")
     _check._chk(t, "targets")
-    B = a.shape[0]
-    K = a.shape[-3]
-    HW = a.shape[-1] * a.shape[-2]
-    a_sb, a_ss = S * K * HW, K * HW
-    if t_mode == "gt":
-        return RowGeom(a, a_sb, a_ss, t, K * HW, 0, 0, 1, B, S, K, HW)
-    if t_mode == "same":
-        return RowGeom(a, a_sb, a_ss, t, a_sb, a_ss, 0, 1, B, S, K, HW)
-    M = t.shape[0]
-    St = t.shape[2] if t.dim() == 6 else 1
-    g = RowGeom(a, a_sb, a_ss, t, St * K * HW, 0, B * St * K * HW, M, B, S, K, HW)
-    g.t_ptr = t.reshape(-1)[(St - 1) * K * HW:]
-    return g
-
-
-def geom_rows(a, a_base_elems, a_sb, t, t_base_elems, t_sb, B, K, HW, t_sm=0, M=1):
-    """Single-stack rows with explicit base offsets/strides (e.g. last-stack slices)."""
-    g = RowGeom(a, a_sb, 0, t, t_sb, 0, t_sm, M, B, 1, K, HW)
-    g.a_ptr = a.reshape(-1)[a_base_elems:]
-    g.t_ptr = t.reshape(-1)[t_base_elems:]
-    return g
-
-
-def row_stats(g, want_amax=False, want_tmax=False):
-    dev = g.a.device
-    rows = g.B * g.S * g.K
-    sq = torch.empty(rows, device=dev, dtype=F32)
-    am = torch.empty(rows, device=dev, dtype=F32) if want_amax else None
-    tm = torch.empty(rows, device=dev, dtype=F32) if want_tmax else None
-    a_sb, a_ss, t_sb, t_ss, t_sm, M, B, S, K, HW = g.args
-    _lib.call("ubpl_heatmap_row_stats", g.a_ptr, a_sb, a_ss, g.t_ptr, t_sb, t_ss, t_sm, M, B, S, K, HW, sq, am, tm)
+    B, S, K, HW, t_sb, t_ss, t_sm, M, _ = rows
+    n = B * S * K
+    sq = torch.empty(n, device=a.device, dtype=F32)
+    am = torch.empty(n, device=a.device, dtype=F32) if want_amax else None
+    tm = torch.empty(n, device=a.device, dtype=F32) if want_tmax else None
+    _lib.call("ubpl_heatmap_row_stats", a, rows.a_sb, rows.a_ss, rows.target(t), t_sb, t_ss, t_sm, M, B, S, K, HW,
+              sq, am, tm)
     return sq, am, tm
 
 
@@ -93,10 +123,11 @@ def loss_finalize(kind, sq, amax, tmax, gate, sw, use_gate, use_sw, B, S, K, thr
     return out_sum, out_cnt, score, w
 
 
-def row_grad(g, w, gscale, extra, da, accumulate=False):
-    a_sb, a_ss, t_sb, t_ss, t_sm, M, B, S, K, HW = g.args
-    _lib.call("ubpl_heatmap_row_grad", g.a_ptr, a_sb, a_ss, g.t_ptr, t_sb, t_ss, t_sm, M, B, S, K, HW, w, gscale,
-              float(extra), da, int(accumulate))
+def row_grad(a, t, rows, w, gscale, extra, da):
+    """da = w[row] * gscale[0] * extra * (a - target) per row of rows (a RowSpec)."""
+    B, S, K, HW, t_sb, t_ss, t_sm, M, _ = rows
+    _lib.call("ubpl_heatmap_row_grad", a, rows.a_sb, rows.a_ss, rows.target(t), t_sb, t_ss, t_sm, M, B, S, K, HW, w,
+              gscale, float(extra), da, 0)
     return da
 
 
@@ -119,20 +150,19 @@ def softmax_peak_scores(x, x_sb, x_ss, x_sm, M, B, S, K, HW, out=None):
     return score
 
 
-def rank_threshold(scores, G, N, rank, out=None):
+def rank_threshold(scores, G, N, rank):
     """thr [G]: the rank-th smallest (0-based) of each group of N in scores [G*N], on the device."""
     _check._chk(scores, "scores")
     if not 1 <= N <= MAX_RANK_GROUP:
         raise ValueError("ubpl_amd: rank_threshold takes groups of 1..%d scores, got %d" % (MAX_RANK_GROUP, N))
     if not 0 <= rank < N:
         raise IndexError("ubpl_amd: rank %d is out of range for a group of %d scores" % (rank, N))
-    thr = torch.empty(G, device=scores.device, dtype=F32) if out is None else out
+    thr = torch.empty(G, device=scores.device, dtype=F32)
     _lib.call("ubpl_rank_threshold", scores, G, N, int(rank), thr)
     return thr
 
 
-def loss_finalize_ranked(kind, sq, ascore, tscore, athr, tthr, gate, sw, use_gate, use_sw, B, S, K,
-                         want_score=True, out=None):
+def loss_finalize_ranked(kind, sq, ascore, tscore, athr, tthr, gate, sw, use_gate, use_sw, B, S, K, want_score=True):
     """loss_finalize for kinds 1 and 2 with given scores and per-stack device thresholds
     -> (sum [1], cnt [4] int32, score [K] or None, w [B*S*K])."""
     dev = sq.device
@@ -140,12 +170,10 @@ def loss_finalize_ranked(kind, sq, ascore, tscore, athr, tthr, gate, sw, use_gat
         raise ValueError("ubpl_amd: loss_finalize_ranked is kind 1 or 2, got %r" % (kind,))
     if tscore is None or tthr is None or (kind == 2 and (ascore is None or athr is None)):
         raise ValueError("ubpl_amd: loss_finalize_ranked kind %d needs its scores and thresholds" % kind)
-    out_sum, out_cnt, score, w = out if out is not None else (None,) * 4
-    out_sum = torch.empty(1, device=dev, dtype=F32) if out_sum is None else out_sum
-    out_cnt = torch.empty(4, device=dev, dtype=torch.int32) if out_cnt is None else out_cnt
-    if score is None and want_score:
-        score = torch.empty(K, device=dev, dtype=F32)
-    w = torch.empty(B * S * K, device=dev, dtype=F32) if w is None else w
+    out_sum = torch.empty(1, device=dev, dtype=F32)
+    out_cnt = torch.empty(4, device=dev, dtype=torch.int32)
+    score = torch.empty(K, device=dev, dtype=F32) if want_score else None
+    w = torch.empty(B * S * K, device=dev, dtype=F32)
     _lib.call("ubpl_loss_finalize_ranked", int(kind), sq, ascore, tscore, athr, tthr, gate, sw, int(use_gate),
               int(use_sw), B, S, K, out_sum, out_cnt, score, w)
     return out_sum, out_cnt, score, w

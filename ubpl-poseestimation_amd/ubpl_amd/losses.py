@@ -18,49 +18,64 @@ from . import _lib
 from . import kernels as Kn
 
 
-def _rows_of(preds, nstack):
-    """(B, S, K, HW) of the reference's reshape((bs, k, -1)) per stack."""
-    B = preds.shape[0]
-    if nstack == 1:
-        K = preds.shape[1]
-        return B, 1, K, preds.numel() // (B * K)
-    K = preds.shape[2]
-    return B, nstack, K, preds.numel() // (B * nstack * K)
-
-
-def _geom(a, S, K, HW, t, t_sb, t_ss, t_sm, M, t_base=0):
-    B = a.shape[0]
-    g = Kn.RowGeom(a, S * K * HW, K * HW, t, t_sb, t_ss, t_sm, M, B, S, K, HW)
-    g.t_ptr = t.reshape(-1)[t_base:]
-    return g
+NO_RULE = ("none", 0.0)
 
 
 class _RowLoss(torch.autograd.Function):
-    """forward: (sum, cnt[4] int32, score[K]) on device; backward: d preds
-    (and d targets for a same-layout target that requires grad)."""
+    """Every heatmap row loss: sum over rows of w_row * mean_px((a - target)^2).
+    rows: a Kn.RowSpec (where each row's target lies).  kind: what the row mask tests —
+    0 nothing, 1 the target's score, 2 both inputs' scores, 3 both and gate > 0 as a row mask
+    (ubpl_loss_finalize's kinds).  rule: what a score is and what it is held to —
+      ("none", 0.0)   kind 0;
+      ("max", v)      the per-map maximum at the constant v;
+      ("softmax", v)  the softmax score (softmax across the keypoint axis at every pixel, then the
+                      per-map maximum: utils/losses.py:137-138) at the constant v;
+      ("rank", r)     the softmax score at, per stack, the r-th smallest of the batch's B*K scores
+                      (folded into the finalize launch, ubpl_loss_finalize_rank).
+    The softmax rules serve kinds 1 and 2; a target that is one map per row for all stacks is
+    scored once.
+    forward: (sum, cnt[4] int32, score[K], thr[2*S]: rateThr1[S] then rateThr2[S]) on the device,
+    no host sync; score is empty for kind 0 (and for kind 1 under a softmax rule), thr for the
+    rules "none" and "max".  backward: d preds (and d targets for a one-member target that
+    requires grad); the mask carries no gradient."""
 
     @staticmethod
-    def forward(ctx, a, t, spec, gate, sw):
-        kind, S, K, HW, tg, use_gate, use_sw, thr = spec
-        g = _geom(a, S, K, HW, t, *tg)
-        sq, am, tm = Kn.row_stats(g, want_amax=(kind in (2, 3)), want_tmax=(kind != 0))
-        s, cnt, score, w = Kn.loss_finalize(kind, sq, am, tm, gate, sw, use_gate, use_sw, a.shape[0], S, K, thr)
+    def forward(ctx, a, t, rows, kind, rule, use_gate, use_sw, gate, sw):
+        B, S, K, HW = rows[:4]
+        how, val = rule
+        thr = None
+        if how in ("none", "max"):
+            sq, am, tm = Kn.row_stats(a, t, rows, want_amax=(kind in (2, 3)), want_tmax=(kind != 0))
+            s, cnt, score, w = Kn.loss_finalize(kind, sq, am, tm, gate, sw, use_gate, use_sw, B, S, K, val)
+        else:
+            sq, _, _ = Kn.row_stats(a, t, rows)
+            St = rows.t_stacks
+            tsc = Kn.softmax_peak_scores(rows.target(t), rows.t_sb, rows.t_ss, rows.t_sm, rows.M, B, St, K, HW)
+            asc = Kn.softmax_peak_scores(a, rows.a_sb, rows.a_ss, 0, 1, B, S, K, HW) if kind == 2 else None
+            if how == "rank":
+                s, cnt, score, w, thr = Kn.loss_finalize_rank(kind, sq, asc, tsc, St, val, gate, sw, use_gate, use_sw,
+                                                              B, S, K, want_score=(kind == 2))
+            else:
+                thr = torch.full((2 * S,), float(val), device=a.device, dtype=torch.float32)
+                if St != S:                                      # the one target score per (b,k) serves every stack
+                    tsc = tsc.view(B, 1, K).expand(B, S, K).contiguous().view(-1)
+                s, cnt, score, w = Kn.loss_finalize_ranked(kind, sq, asc, tsc, thr[:S] if kind == 2 else None, thr[S:],
+                                                           gate, sw, use_gate, use_sw, B, S, K, want_score=(kind == 2))
         ctx.save_for_backward(a, t, w)
-        ctx.spec = spec
-        ctx.t_grad = t.requires_grad and tg[3] == 1 and tg[2] == 0
-        outs = (s.view(()), cnt) + ((score,) if score is not None else (s.new_empty(0),))
+        ctx.rows = rows
+        ctx.t_grad = t.requires_grad and rows.M == 1 and rows.t_sm == 0
+        outs = (s.view(()), cnt, score if score is not None else s.new_empty(0),
+                thr if thr is not None else s.new_empty(0))
         ctx.mark_non_differentiable(*outs[1:])
         return outs
 
     @staticmethod
-    def backward(ctx, gs, _gc, _gsc):
+    def backward(ctx, gs, *_):
         a, t, w = ctx.saved_tensors
-        kind, S, K, HW, tg, _, _, _ = ctx.spec
-        g = _geom(a, S, K, HW, t, *tg)
         da = torch.empty_like(a)
-        Kn.row_grad(g, w, gs.reshape(1).contiguous().float(), 2.0 / HW, da)
+        Kn.row_grad(a, t, ctx.rows, w, gs.reshape(1).contiguous().float(), 2.0 / ctx.rows.HW, da)
         dt = -da if ctx.t_grad else None
-        return da, dt, None, None, None
+        return (da, dt) + (None,) * 7
 
 
 def _f32c(t):
@@ -87,6 +102,15 @@ def _sw_vec(sw):
     return None if sw is None else sw.detach().float().reshape(-1).contiguous()
 
 
+def _gated_sum(mod, a, t, rows, kpsGate, sampleWeight):
+    """The unmasked losses' common end -> (sum, nStack*#{gate>0})."""
+    gate, count = _gate_rows(kpsGate, rows.B, rows.K, rows.S)
+    sw = _sw_vec(sampleWeight) if mod.useSampleWeight else None
+    s, cnt, _, _ = _RowLoss.apply(a, t, rows, 0, NO_RULE, bool(mod.useKPsGate and gate is not None), sw is not None,
+                                  gate, sw)
+    return s, count if count is not None else int(cnt[0].item())
+
+
 class JointMSELoss(nn.Module):
     """utils/losses.py:8-29 -> (sum over stacks/rows of the per-map pixel mean, nStack*#{gate>0})."""
 
@@ -97,16 +121,11 @@ class JointMSELoss(nn.Module):
     def forward(self, preds, gts, kpsGate=None, sampleWeight=None):
         _lib.require_gpu(preds)
         a = preds.contiguous()
-        B, S, K, HW = _rows_of(a, self.nStack)
+        rows = Kn.RowSpec.ground_truth(*Kn.pred_rows(a, self.nStack))
         t = gts.detach().contiguous()
-        if t.numel() != B * K * HW:
+        if t.numel() != rows.B * rows.K * rows.HW:
             raise RuntimeError("gts do not match preds rows")
-        gate, count = _gate_rows(kpsGate, B, K, S)
-        sw = _sw_vec(sampleWeight) if self.useSampleWeight else None
-        spec = (0, S, K, HW, (K * HW, 0, 0, 1), bool(self.useKPsGate and gate is not None),
-                bool(self.useSampleWeight and sw is not None), 0.0)
-        s, cnt, _ = _RowLoss.apply(a, t, spec, gate, sw)
-        return s, count if count is not None else int(cnt[0].item())
+        return _gated_sum(self, a, t, rows, kpsGate, sampleWeight)
 
 
 class JointDistLoss(nn.Module):
@@ -119,14 +138,18 @@ class JointDistLoss(nn.Module):
     def forward(self, preds1, preds2, kpsGate=None, sampleWeight=None):
         _lib.require_gpu(preds1)
         a = preds1.contiguous()
-        B, S, K, HW = _rows_of(a, self.nStack)
+        rows = Kn.RowSpec.same(*Kn.pred_rows(a, self.nStack))
         t = preds2.contiguous()
-        gate, count = _gate_rows(kpsGate, B, K, S)
-        sw = _sw_vec(sampleWeight) if self.useSampleWeight else None
-        spec = (0, S, K, HW, (S * K * HW, K * HW, 0, 1), bool(self.useKPsGate and gate is not None),
-                bool(self.useSampleWeight and sw is not None), 0.0)
-        s, cnt, _ = _RowLoss.apply(a, t, spec, gate, sw)
-        return s, count if count is not None else int(cnt[0].item())
+        return _gated_sum(self, a, t, rows, kpsGate, sampleWeight)
+
+
+def _some_rows(cnt):
+    """cnt[4] on the host; no row with sampleWeight > 0 raises as the reference's torch.stack of an
+    empty list does (utils/losses.py:107,157,201,279)."""
+    c = cnt.tolist()
+    if c[3] == 0:
+        raise RuntimeError("stack expects a non-empty TensorList")
+    return c
 
 
 class JointDistLoss_mt2(nn.Module):
@@ -141,19 +164,31 @@ class JointDistLoss_mt2(nn.Module):
     def forward(self, preds1, preds2, kpsGate=None, sampleWeight=None):
         _lib.require_gpu(preds1)
         a = preds1.contiguous()
-        B, S, K, HW = _rows_of(a, self.nStack)
+        rows = Kn.RowSpec.same(*Kn.pred_rows(a, self.nStack))
         t = preds2.contiguous()
         gate = _f32c(kpsGate)
         sw = _sw_vec(sampleWeight)
-        use_sw = bool(self.useSampleWeight and sw is not None)
-        spec = (1, S, K, HW, (S * K * HW, K * HW, 0, 1), bool(self.useKPsGate and gate is not None), use_sw,
-                float(self.scoreThr))
-        # rows feeding the score are those with sampleWeight > 0 (utils/losses.py:276)
-        s, cnt, score = _RowLoss.apply(a, t, spec, gate, sw if use_sw else sw)
-        c = cnt.tolist()
-        if c[3] == 0:
-            raise RuntimeError("stack expects a non-empty TensorList")  # utils/losses.py:279
+        # rows feeding the score are those with sampleWeight > 0 (utils/losses.py:276), weighted or not
+        s, cnt, score, _ = _RowLoss.apply(a, t, rows, 1, ("max", float(self.scoreThr)),
+                                          bool(self.useKPsGate and gate is not None),
+                                          bool(self.useSampleWeight and sw is not None), gate, sw)
+        c = _some_rows(cnt)
         return s, c[0], c[1], c[2], score
+
+
+def _pseudo_rows(mod, preds, targets, sampleWeight, rule):
+    """The ensemble pseudo-label losses' common body: targets [M,B,St,K,R,R] ([M,B,K,R,R] with
+    nStack == 1), the member mean of the last stack against every stack of preds, both inputs'
+    scores under `rule` -> (sum, n_pseudo, n_sel, score[K], rateThr1[S], rateThr2[S]; empty
+    under the "max" rule)."""
+    _lib.require_gpu(preds)
+    a = preds.contiguous()
+    B, S, K, HW = Kn.pred_rows(a, mod.nStack)
+    t = targets.detach().contiguous()
+    rows = Kn.RowSpec.ensemble(B, S, K, HW, t.shape[0], 1 if mod.nStack == 1 else t.shape[2])
+    s, cnt, score, thr = _RowLoss.apply(a, t, rows, 2, rule, False, True, None, _sw_vec(sampleWeight))
+    c = _some_rows(cnt)
+    return s, c[1], c[2], score, thr[:S], thr[S:]
 
 
 class JointPseudoLoss3(nn.Module):
@@ -165,25 +200,8 @@ class JointPseudoLoss3(nn.Module):
         self.nStack, self.scoreThr = nStack, scoreThr
 
     def forward(self, preds, targets, sampleWeight):
-        _lib.require_gpu(preds)
-        a = preds.contiguous()
-        B, S, K, HW = _rows_of(a, self.nStack)
-        t = targets.detach().contiguous()
-        M = t.shape[0]
-        if self.nStack == 1:
-            tg = (K * HW, 0, t.numel() // M, M)
-            base = 0
-        else:
-            St = t.shape[2]
-            tg = (St * K * HW, 0, B * St * K * HW, M)
-            base = (St - 1) * K * HW
-        sw = _sw_vec(sampleWeight)
-        spec = (2, S, K, HW, tg + (base,), False, True, float(self.scoreThr))
-        s, cnt, score = _RowLoss.apply(a, t, spec, None, sw)
-        c = cnt.tolist()
-        if c[3] == 0:
-            raise RuntimeError("stack expects a non-empty TensorList")  # utils/losses.py:201
-        return s, c[1], c[2], score, self.scoreThr, self.scoreThr
+        out = _pseudo_rows(self, preds, targets, sampleWeight, ("max", float(self.scoreThr)))
+        return out[:4] + (self.scoreThr, self.scoreThr)
 
 
 def sel_rank(n, selRate):
@@ -192,74 +210,13 @@ def sel_rank(n, selRate):
     return int(n * (1 - selRate))
 
 
-class _RankedRowLoss(torch.autograd.Function):
-    """_RowLoss with the reference's softmax scores in the mask (utils/losses.py:73-166, 213-243).
-    spec = (kind, S, K, HW, tg, use_gate, use_sw, sel): tg as _RowLoss's; sel = ("rank", r): per
-    stack the r-th smallest of the batch's B*K scores is the threshold (folded into the finalize
-    launch, ubpl_loss_finalize_rank), or ("thr", v): the constant v.  kind 2 masks by the scores of
-    both inputs, kind 1 by the second's.  A target that is one map per row for all stacks
-    (t_ss == 0) is scored once.
-    forward: (sum, cnt[4] int32, score[K], thr[2*S]: rateThr1[S] then rateThr2[S]) on the device,
-    no host sync."""
-
-    @staticmethod
-    def forward(ctx, a, t, spec, gate, sw):
-        kind, S, K, HW, tg, use_gate, use_sw, sel = spec
-        B = a.shape[0]
-        g = _geom(a, S, K, HW, t, *tg)
-        sq, _, _ = Kn.row_stats(g)
-        t_sb, t_ss, t_sm, M = tg[:4]
-        St = 1 if t_ss == 0 else S
-        tsc = Kn.softmax_peak_scores(g.t_ptr, t_sb, t_ss, t_sm, M, B, St, K, HW)
-        asc = Kn.softmax_peak_scores(a, S * K * HW, K * HW, 0, 1, B, S, K, HW) if kind == 2 else None
-        if sel[0] == "rank":
-            s, cnt, score, w, thr = Kn.loss_finalize_rank(kind, sq, asc, tsc, St, sel[1], gate, sw, use_gate, use_sw,
-                                                          B, S, K, want_score=(kind == 2))
-        else:
-            thr = torch.full((2 * S,), float(sel[1]), device=a.device, dtype=torch.float32)
-            if St != S:                                      # the one target score per (b,k) serves every stack
-                tsc = tsc.view(B, 1, K).expand(B, S, K).contiguous().view(-1)
-            s, cnt, score, w = Kn.loss_finalize_ranked(kind, sq, asc, tsc, thr[:S] if kind == 2 else None, thr[S:],
-                                                       gate, sw, use_gate, use_sw, B, S, K, want_score=(kind == 2))
-        ctx.save_for_backward(a, t, w)
-        ctx.spec = spec
-        ctx.t_grad = t.requires_grad and tg[3] == 1 and tg[2] == 0
-        outs = (s.view(()), cnt, score if score is not None else s.new_empty(0), thr)
-        ctx.mark_non_differentiable(*outs[1:])
-        return outs
-
-    @staticmethod
-    def backward(ctx, gs, *_):
-        a, t, w = ctx.saved_tensors
-        _, S, K, HW, tg = ctx.spec[:5]
-        g = _geom(a, S, K, HW, t, *tg)
-        da = torch.empty_like(a)
-        Kn.row_grad(g, w, gs.reshape(1).contiguous().float(), 2.0 / HW, da)
-        dt = -da if ctx.t_grad else None
-        return da, dt, None, None, None
-
-
-def _ens_geom(t, nstack, B, K, HW):
-    """Target strides of an ensemble stack [M,B,(St,)K,R,R]: the mean over M of the last stack."""
-    M = t.shape[0]
-    if nstack == 1:
-        return (K * HW, 0, t.numel() // M, M, 0)
-    St = t.shape[2]
-    return (St * K * HW, 0, B * St * K * HW, M, (St - 1) * K * HW)
-
-
-def _pseudo_ranked(mod, preds, targets, sampleWeight, sel):
-    _lib.require_gpu(preds)
-    a = preds.contiguous()
-    B, S, K, HW = _rows_of(a, mod.nStack)
-    t = targets.detach().contiguous()
-    sw = _sw_vec(sampleWeight)
-    spec = (2, S, K, HW, _ens_geom(t, mod.nStack, B, K, HW), False, True, sel)
-    s, cnt, score, thr = _RankedRowLoss.apply(a, t, spec, None, sw)
-    c = cnt.tolist()
-    if c[3] == 0:
-        raise RuntimeError("stack expects a non-empty TensorList")  # utils/losses.py:107,157
-    return s, c[1], c[2], score, thr[:S], thr[S:]
+def _batch_rank(preds, nstack, selRate):
+    """sel_rank over the batch's B*K scores, out of range as the reference's indexing raises it."""
+    B, _, K, _ = Kn.pred_rows(preds, nstack)
+    rank = sel_rank(B * K, selRate)
+    if not 0 <= rank < B * K:
+        raise IndexError("index %d is out of bounds for dimension 0 with size %d" % (rank, B * K))
+    return rank
 
 
 class JointPseudoLoss(nn.Module):
@@ -273,7 +230,7 @@ class JointPseudoLoss(nn.Module):
         self.nStack, self.scoreThr = nStack, scoreThr
 
     def forward(self, preds, targets, sampleWeight):
-        return _pseudo_ranked(self, preds, targets, sampleWeight, ("thr", float(self.scoreThr)))[:4]
+        return _pseudo_rows(self, preds, targets, sampleWeight, ("softmax", float(self.scoreThr)))[:4]
 
 
 class JointPseudoLoss2(nn.Module):
@@ -291,11 +248,8 @@ class JointPseudoLoss2(nn.Module):
         self.nStack, self.selRate = nStack, selRate
 
     def forward(self, preds, targets, sampleWeight):
-        B, _, K, _ = _rows_of(preds, self.nStack)
-        rank = sel_rank(B * K, self.selRate)
-        if not 0 <= rank < B * K:
-            raise IndexError("index %d is out of bounds for dimension 0 with size %d" % (rank, B * K))
-        return _pseudo_ranked(self, preds, targets, sampleWeight, ("rank", rank))
+        rank = _batch_rank(preds, self.nStack, self.selRate)
+        return _pseudo_rows(self, preds, targets, sampleWeight, ("rank", rank))
 
 
 class JointDistLoss_mt(nn.Module):
@@ -309,16 +263,14 @@ class JointDistLoss_mt(nn.Module):
     def forward(self, preds1, preds2, kpsGate=None, sampleWeight=None):
         _lib.require_gpu(preds1)
         a = preds1.contiguous()
-        B, S, K, HW = _rows_of(a, self.nStack)
-        rank = sel_rank(B * K, self.selRate)
-        if not 0 <= rank < B * K:
-            raise IndexError("index %d is out of bounds for dimension 0 with size %d" % (rank, B * K))
+        rank = _batch_rank(a, self.nStack, self.selRate)
+        rows = Kn.RowSpec.same(*Kn.pred_rows(a, self.nStack))
         t = preds2.contiguous()
         gate = _f32c(kpsGate)
         sw = _sw_vec(sampleWeight)
-        spec = (1, S, K, HW, (S * K * HW, K * HW, 0, 1), bool(self.useKPsGate and gate is not None),
-                bool(self.useSampleWeight and sw is not None), ("rank", rank))
-        s, cnt, _, _ = _RankedRowLoss.apply(a, t, spec, gate, sw)
+        s, cnt, _, _ = _RowLoss.apply(a, t, rows, 1, ("rank", rank),
+                                      bool(self.useKPsGate and gate is not None),
+                                      bool(self.useSampleWeight and sw is not None), gate, sw)
         return s, int(cnt[0].item())
 
 
@@ -330,9 +282,8 @@ class JointFeatureDistLoss(nn.Module):
         bs, n, c = inp1.shape[:3]
         a = inp1.contiguous()
         t = inp2.contiguous()
-        HW = a.numel() // (bs * n * c)
-        spec = (0, 1, n * c, HW, (n * c * HW, 0, 0, 1), False, False, 0.0)
-        s, _, _ = _RowLoss.apply(a, t, spec, None, None)
+        rows = Kn.RowSpec.flat(bs, n * c, a.numel() // (bs * n * c))
+        s, _, _, _ = _RowLoss.apply(a, t, rows, 0, NO_RULE, False, False, None, None)
         return s, bs * n
 
 

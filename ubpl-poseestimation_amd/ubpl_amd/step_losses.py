@@ -4,77 +4,68 @@ section of each train.py step (between the networks' forwards and the backward)
 builds its sums, counts and FDL views from these; _RecordLayout says where they go."""
 import torch
 
-from .losses import _RankedRowLoss, _RowLoss, features_cov
+from . import kernels as Kn
+from .losses import NO_RULE, _RowLoss, features_cov
 from .process import render_batch
+
+
+def _stacked(preds, S):
+    """(B, S, K, HW) of [B,S,K,R,R] predictions: a row per (sample, stack, keypoint)."""
+    return preds.shape[0], S, preds.shape[2], preds.shape[-1] * preds.shape[-2]
 
 
 def _mse(preds, gts, S, gate, sw):
     """JointMSELoss(nStack=S, useKPsGate=True, useSampleWeight=True): (sum, cnt[4])."""
-    K = preds.shape[2]
-    HW = preds.shape[-1] * preds.shape[-2]
-    spec = (0, S, K, HW, (K * HW, 0, 0, 1), gate is not None, sw is not None, 0.0)
-    s, c, _ = _RowLoss.apply(preds, gts, spec, gate, sw)
-    return s, c
+    rows = Kn.RowSpec.ground_truth(*_stacked(preds, S))
+    return _RowLoss.apply(preds, gts, rows, 0, NO_RULE, gate is not None, sw is not None, gate, sw)[:2]
 
 
 def _mse_plain(preds, gts, S):
     """JointMSELoss(nStack=S) without gate/weights (projects/supervised.py:138);
-    nStack == 1 keeps the reference's per-sample rows (reshape((bs, k, -1)))."""
-    B = preds.shape[0]
-    if S == 1:
-        K = preds.shape[1]
-        HW = preds.numel() // (B * K)
-        spec = (0, 1, K, HW, (K * HW, 0, 0, 1), False, False, 0.0)
-    else:
-        K = preds.shape[2]
-        HW = preds.shape[-1] * preds.shape[-2]
-        spec = (0, S, K, HW, (K * HW, 0, 0, 1), False, False, 0.0)
-    s, c, _ = _RowLoss.apply(preds, gts, spec, None, None)
-    return s, c
+    nStack == 1 keeps the reference's per-sample rows (Kn.pred_rows)."""
+    rows = Kn.RowSpec.ground_truth(*Kn.pred_rows(preds, S))
+    return _RowLoss.apply(preds, gts, rows, 0, NO_RULE, False, False, None, None)[:2]
+
+
+def _last_pair(preds, tpreds):
+    """The last stacks of both, contiguous, and their same-layout rows."""
+    a = preds[:, -1].contiguous()
+    t = tpreds[:, -1].contiguous()
+    return a, t, Kn.RowSpec.same(a.shape[0], 1, a.shape[1], a.shape[-1] * a.shape[-2])
 
 
 def _dist_last(preds, tpreds):
     """JointDistLoss() on the last stack of both (projects/MT_UBPL.py:250)."""
-    a = preds[:, -1].contiguous()
-    t = tpreds[:, -1].contiguous()
-    K = a.shape[1]
-    HW = a.shape[-1] * a.shape[-2]
-    spec = (0, 1, K, HW, (K * HW, K * HW, 0, 1), False, False, 0.0)
-    s, c, _ = _RowLoss.apply(a, t, spec, None, None)
-    return s, c
+    a, t, rows = _last_pair(preds, tpreds)
+    return _RowLoss.apply(a, t, rows, 0, NO_RULE, False, False, None, None)[:2]
 
 
 def _dist_mt2_last(preds, tpreds, sw, thr):
     """JointDistLoss_mt2(useSampleWeight=True, scoreThr) on the last stacks
     (projects/DualPose_UBPL.py:163,203)."""
-    a = preds[:, -1].contiguous()
-    t = tpreds[:, -1].contiguous()
-    K = a.shape[1]
-    HW = a.shape[-1] * a.shape[-2]
-    spec = (1, 1, K, HW, (K * HW, K * HW, 0, 1), False, True, float(thr))
-    return _RowLoss.apply(a, t, spec, None, sw)
+    a, t, rows = _last_pair(preds, tpreds)
+    return _RowLoss.apply(a, t, rows, 1, ("max", float(thr)), False, True, None, sw)[:3]
+
+
+def _ens_rows(preds, targets, S):
+    """Rows of preds [B,S,K,R,R] against the ensemble targets [M,B,St,K,R,R]."""
+    return Kn.RowSpec.ensemble(*_stacked(preds, S), targets.shape[0], targets.shape[2])
 
 
 def _pseudo(preds, targets, sw, S, thr):
     """JointPseudoLoss3(nStack=S, scoreThr) with targets [M,B,S,K,R,R]."""
-    B, K = preds.shape[0], preds.shape[2]
-    HW = preds.shape[-1] * preds.shape[-2]
-    M, St = targets.shape[0], targets.shape[2]
-    spec = (2, S, K, HW, (St * K * HW, 0, B * St * K * HW, M, (St - 1) * K * HW), False, True, float(thr))
-    return _RowLoss.apply(preds, targets, spec, None, sw)
+    return _RowLoss.apply(preds, targets, _ens_rows(preds, targets, S), 2, ("max", float(thr)), False, True, None,
+                          sw)[:3]
 
 
 def _pseudo_gated(preds, targets, sw, S, thr, gate):
     """_pseudo with a given selection (ubpl_loss_finalize kind 3): gate [B,K] device float32, > 0 =
     the joint's pseudo label is kept; the row mask is gate * the two score tests at thr
     (thr = -inf: the gate alone; a NaN score still never selects)."""
-    B, K = preds.shape[0], preds.shape[2]
-    HW = preds.shape[-1] * preds.shape[-2]
-    M, St = targets.shape[0], targets.shape[2]
-    if gate is None or gate.numel() != B * K:
-        raise ValueError("ubpl_amd: _pseudo_gated takes a gate of [B,K] = %d x %d entries" % (B, K))
-    spec = (3, S, K, HW, (St * K * HW, 0, B * St * K * HW, M, (St - 1) * K * HW), False, True, float(thr))
-    return _RowLoss.apply(preds, targets, spec, gate, sw)
+    rows = _ens_rows(preds, targets, S)
+    if gate is None or gate.numel() != rows.B * rows.K:
+        raise ValueError("ubpl_amd: _pseudo_gated takes a gate of [B,K] = %d x %d entries" % (rows.B, rows.K))
+    return _RowLoss.apply(preds, targets, rows, 3, ("max", float(thr)), False, True, gate, sw)[:3]
 
 
 def _pseudo_ranked(preds, targets, sw, S, rank):
@@ -82,11 +73,7 @@ def _pseudo_ranked(preds, targets, sw, S, rank):
     each input's softmax score >= the rank-th smallest of the batch's B*K (rank a host integer,
     losses.sel_rank) -> (sum, cnt[4], score[K], thr[2*S]: rateThr1[S] then rateThr2[S]), all on the
     device; the rank selections run inside the finalize launch (ubpl_loss_finalize_rank)."""
-    B, K = preds.shape[0], preds.shape[2]
-    HW = preds.shape[-1] * preds.shape[-2]
-    M, St = targets.shape[0], targets.shape[2]
-    spec = (2, S, K, HW, (St * K * HW, 0, B * St * K * HW, M, (St - 1) * K * HW), False, True, ("rank", int(rank)))
-    return _RankedRowLoss.apply(preds, targets, spec, None, sw)
+    return _RowLoss.apply(preds, targets, _ens_rows(preds, targets, S), 2, ("rank", int(rank)), False, True, None, sw)
 
 
 def _norm(s, n):
@@ -112,9 +99,9 @@ def _fdl_view(fa, fb, rowmask, args):
         n = c.float()
         return "cov", torch.where(n[0] > 0, v, torch.zeros_like(v)), n
     B, S, C = fa.shape[:3]
-    HW = fa[0, 0, 0].numel()
-    spec = (0, 1, S * C, HW, (S * C * HW, 0, 0, 1), False, True, 0.0)
-    s, _, _ = _RowLoss.apply(fa.contiguous(), fb.contiguous(), spec, None, rowmask.reshape(-1).contiguous())
+    rows = Kn.RowSpec.flat(B, S * C, fa[0, 0, 0].numel())
+    s = _RowLoss.apply(fa.contiguous(), fb.contiguous(), rows, 0, NO_RULE, False, True, None,
+                       rowmask.reshape(-1).contiguous())[0]
     return "dist", s, ((rowmask > 0).sum() * S).float().reshape(1)
 
 
